@@ -2,7 +2,12 @@
 """bench.py — the headline benchmark of BASELINE.json: Mpaths/s (+ Mrays/s) of the 1080p, 8-bounce,
 871,200-triangle dragon Cornell box (config C3), on N GPUs of one node.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config C3]
+  python bench.py [--gpus N --steps K --warmup W] [--config C3] [--full] [--dump-outputs DIR]
+  A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, the roofline of the timed
+  launches).  --full adds every other leg described below: the counting replay (Mrays/s, primary_miss_frac, logical
+  bytes), "framed", per_frame, camera_move, fast_bvh, cpu_baseline and, at N > 1, the strong-scaling leg and the
+  cross-check gather.  --dump-outputs DIR writes the timed region's final image to DIR/image.npy (float32, H x W x 4;
+  above 64 MB a fixed seeded sample of its pixels, dump_array).
   (N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N; run without
   a launcher, `python bench.py --gpus N` starts that launcher itself as a child process, before anything touches a GPU,
   and relays rank 0's line and the exit status)
@@ -697,11 +702,36 @@ def cpu_baseline(packed, params, cube, width, height, seconds, threads):
                       f"({host['physical_cores_in_affinity']} physical cores)"}
 
 
-def main():
+DUMP_CAP_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much
+
+
+def dump_array(img: np.ndarray, cap_bytes: int = DUMP_CAP_BYTES) -> np.ndarray:
+    """What --dump-outputs stores of the image: all of it as float32 (H, W, 4) when that fits in `cap_bytes` (C3 at
+    1080p: 33 MB), else a fixed sample of its pixels, (n, 4): n pixel indices drawn without replacement by a generator
+    seeded with 0, in ascending order, the same for every image of one size."""
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes <= cap_bytes:
+        return img
+    flat = img.reshape(-1, img.shape[-1])
+    n = cap_bytes // (4 * flat.shape[1])
+    return flat[np.sort(np.random.default_rng(0).choice(flat.shape[0], size=n, replace=False))]
+
+
+def parse_args(argv=None):
+    """The command line; a run without --full has every leg beside the headline switched off."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=3)  # both trace streams sort a cost order before the timed launches
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline: the counting replay (Mrays/s, counters, logical bytes), the "
+                         "per-frame, camera-move, framed and SAH legs, the CPU baseline, and at N > 1 / --emulate-ranks "
+                         "the strong-scaling leg and the cross-check gather (each can still be skipped with its --no-... "
+                         "option); without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the image the timed region left in the accumulator (what "
+                         "hg_readback returns to a caller; N > 1: the gathered image) as DIR/image.npy, float32 (H, W, 4); "
+                         "an image above 64 MB (C4) is stored as a fixed seeded sample of its pixels, (n, 4)")
     ap.add_argument("--config", default="C3", choices=sorted(scenes.CONFIGS))
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
@@ -758,13 +788,22 @@ def main():
     ap.add_argument("--dist-probe", action="store_true",
                     help="launcher check, no GPU: every rank joins the process group, all-reduces its rank, rank 0 prints "
                          "one JSON line (tests/test_bench_launch.py)")
-    ap.add_argument("--detail-out", default="gpurun_out/bench_detail.json",
+    ap.add_argument("--detail-out", default="bench_out/bench_detail.json",
                     help="the per-format display tables and other bulky legs (the line keeps a compact summary)")
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="1-GPU rehearsal of one rank's share at N ranks (tiles t %% N == 0, N*fps frames); "
                          "reports that rank's own Mpaths/s, not a contract line")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline figure only, every other leg is --full's
+        args.no_counters = args.no_per_frame = args.no_framed = args.no_fast_bvh = args.no_cpu_baseline = True
+        args.no_strong = args.no_abi_check = True
+    return args
 
+
+def main():
+    args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     emu = args.emulate_ranks if world == 1 and args.emulate_ranks > 1 else 0
@@ -1058,7 +1097,8 @@ def main():
     timing = ctx.counters()  # kernel_ms / launches of the timed launches
     kernel_symbol = KERNEL_SYMBOL.get(int(timing["last_kernel"]), "?")  # the variant HG_KERNEL_AUTO resolved to
     replay_identical = None
-    timed_img = ctx.readback(W, H) if world == 1 and (not args.no_counters or args.save_image) else None
+    timed_img = ctx.readback(W, H) if world == 1 and (not args.no_counters or args.save_image
+                                                      or args.dump_outputs) else None
     if not args.no_counters:
         # Counting replay, untimed: the same K steps from the same cleared state with the device counters on give
         # the exact traversal counts of the timed launches (the render is deterministic — checked on the image).
@@ -1191,10 +1231,14 @@ def main():
                           "trace_launches": cnt["trace_launches"]},
             "cpu_baseline": None,
         }
-        if args.save_image:
+        if args.save_image or args.dump_outputs:
             img = (gathered if isinstance(gathered, np.ndarray) else gathered.cpu().numpy()) if gathered is not None \
                 else timed_img
+        if args.save_image:
             np.save(args.save_image, img)
+        if args.dump_outputs:  # the timed region's image, as a caller of hg_render + hg_readback receives it
+            Path(args.dump_outputs).mkdir(parents=True, exist_ok=True)
+            np.save(Path(args.dump_outputs) / "image.npy", dump_array(img))
         if world == 1 and not emu and not args.no_per_frame:
             result["per_frame"] = per_frame_measurement(ctx, params, W, H, frames_per_step, max(2, args.steps),
                                                         result["value"])

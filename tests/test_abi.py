@@ -22,7 +22,7 @@ def test_reference_struct_sizes(built):
         assert C.sizeof(getattr(abi, name)) == size, name
 
 
-def _c_layout():
+def _c_layout(tmp_path):
     """sizeof/offsetof of every ABI struct field as compiled by gcc from the header."""
     structs = {"HalogenSphere": abi.HalogenSphere, "HalogenMeshData": abi.HalogenMeshData,
                "PackedRayMedium": abi.PackedRayMedium, "PackedHalogenMaterial": abi.PackedHalogenMaterial,
@@ -34,9 +34,9 @@ def _c_layout():
         for f, _ in py._fields_:
             lines.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
     lines.append("return 0;}")
-    src = Path("/tmp/hg_layout_probe.c")
+    src = tmp_path / "hg_layout_probe.c"
     src.write_text("\n".join(lines))
-    exe = Path("/tmp/hg_layout_probe")
+    exe = tmp_path / "hg_layout_probe"
     subprocess.run(["gcc", "-I", str(ROOT / "include"), str(src), "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
     res = {}
@@ -46,8 +46,8 @@ def _c_layout():
     return structs, res
 
 
-def test_ctypes_mirror_matches_header(built):
-    structs, res = _c_layout()
+def test_ctypes_mirror_matches_header(built, tmp_path):
+    structs, res = _c_layout(tmp_path)
     for cname, py in structs.items():
         assert C.sizeof(py) == res[(cname, "size")], cname
         for f, _ in py._fields_:

@@ -6,7 +6,6 @@ scene records of HalogenStructs.cs field-for-field equal to the header's structs
 build image, so these textual checks stand in for compiling the binding."""
 import json
 import re
-import subprocess
 import sys
 from pathlib import Path
 
@@ -68,11 +67,3 @@ def cs_fields(name):
 def test_record_structs_match_header(name):
     assert cs_fields(name) == c_fields(name)
     assert re.search(r"\[StructLayout\(LayoutKind\.Sequential\)\]\s*public struct %s\b" % name, STRUCTS), name
-
-
-@pytest.mark.skipif(not Path("/root/reference/Assets").exists(), reason="reference checkout absent (GPU box)")
-def test_fixture_equals_fresh_extraction(tmp_path):
-    out = tmp_path / "s.json"
-    subprocess.run([sys.executable, str(ROOT / "tools" / "extract_csharp_surface.py"), "--out", str(out)], check=True,
-                   capture_output=True)
-    assert json.loads(out.read_text()) == json.loads(FIXTURE.read_text())

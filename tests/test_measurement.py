@@ -69,6 +69,43 @@ def test_roofline_prices_the_binding_unit(bench, monkeypatch):
     assert r["bound"] == "valu" and r["frac"] == pytest.approx(26.92 / 0.0384 / 1228.8)
 
 
+LEG_SWITCHES = ("no_counters", "no_per_frame", "no_framed", "no_fast_bvh", "no_cpu_baseline", "no_strong",
+                "no_abi_check")
+
+
+def test_plain_run_switches_every_other_leg_off(bench):
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs == ""
+    assert all(getattr(a, k) for k in LEG_SWITCHES)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d" and not any(getattr(a, k) for k in LEG_SWITCHES)
+    a = bench.parse_args(["--full", "--no-framed", "--no-cpu-baseline"])  # the --no-... options prune --full
+    assert [k for k in LEG_SWITCHES if getattr(a, k)] == ["no_framed", "no_cpu_baseline"]
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--steps", "-1"], ["--warmup", "-1"]])
+def test_step_counts_are_checked(bench, argv):
+    with pytest.raises(SystemExit):
+        bench.parse_args(argv)
+
+
+def test_dump_array_keeps_the_image_or_a_fixed_sample(bench):
+    import numpy as np
+
+    img = np.arange(30 * 50 * 4, dtype=np.float64).reshape(30, 50, 4)
+    whole = bench.dump_array(img, cap_bytes=30 * 50 * 16)  # exactly at the cap: the image itself, as float32
+    assert whole.dtype == np.float32 and whole.shape == (30, 50, 4) and np.array_equal(whole, img)
+    part = bench.dump_array(img, cap_bytes=30 * 50 * 16 - 1)
+    assert part.dtype == np.float32 and part.shape == (30 * 50 - 1, 4) and part.nbytes <= 30 * 50 * 16 - 1
+    pix = (part[:, 0] / 4).astype(int)  # channel 0 of pixel p holds 4 p: the sampled pixels, distinct and ascending
+    assert (np.diff(pix) > 0).all() and np.array_equal(part, img.reshape(-1, 4)[pix])
+    assert np.array_equal(part, bench.dump_array(img.copy(), cap_bytes=30 * 50 * 16 - 1))  # the same sample every time
+    small = bench.dump_array(img, cap_bytes=1600)
+    assert small.shape == (100, 4)
+    assert bench.DUMP_CAP_BYTES <= 64 * 1000 * 1000
+    assert 3840 * 2160 * 16 > bench.DUMP_CAP_BYTES >= 1920 * 1080 * 16  # C4 is sampled, the headline's 1080p is whole
+
+
 def test_committed_bench_line_keeps_the_contract():
     """The round's committed bench line (profiles/r06f_bench.json, the shipped library on the GPU box) carries the
     driver's contract keys, the roofline priced on the vector-memory unit from the committed profile of the same

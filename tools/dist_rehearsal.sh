@@ -5,7 +5,7 @@
 set -u
 mkdir -p gpurun_out/dist
 export HALOGEN_BENCH_DEVICE=0
-ARGS="--config C3 --width 640 --height 360 --steps 1 --warmup 1 --no-cpu-baseline --frames-per-step 8"
+ARGS="--full --config C3 --width 640 --height 360 --steps 1 --warmup 1 --no-cpu-baseline --frames-per-step 8"
 for n in 2 3; do
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
       --master-port $((29500 + n)) bench.py --gpus $n --dist-backend gloo --gather torch --no-abi-check $ARGS \

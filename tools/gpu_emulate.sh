@@ -6,7 +6,7 @@ O=gpurun_out/emulate
 mkdir -p $O
 for n in ${RANKS:-2 4 8}; do
   for f in ${FILLS:-0 4}; do
-    timeout -k 10 240 python bench.py --emulate-ranks $n --queue-fill $f --no-per-frame --no-cpu-baseline --no-framed \
+    timeout -k 10 240 python bench.py --full --emulate-ranks $n --queue-fill $f --no-per-frame --no-cpu-baseline --no-framed \
         --no-fast-bvh --steps ${STEPS:-8} ${EXTRA:-} > $O/n${n}_f${f}.json 2> $O/n${n}_f${f}.err || { tail -5 $O/n${n}_f${f}.err; exit 1; }
     python3 -c "
 import json; r = json.loads(open('$O/n${n}_f${f}.json').read().strip().splitlines()[-1]); s = r['strong_scaling']

@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/launch
 mkdir -p $O
-ARGS="--config C3 --width 640 --height 360 --steps 1 --warmup 1 --no-cpu-baseline --frames-per-step 8 --gather torch --no-abi-check"
+ARGS="--full --config C3 --width 640 --height 360 --steps 1 --warmup 1 --no-cpu-baseline --frames-per-step 8 --gather torch --no-abi-check"
 HALOGEN_BENCH_DEVICE=0 timeout -k 10 300 python3 bench.py --gpus 2 --dist-backend gloo $ARGS --save-image $O/img_n2.npy \
     > $O/n2.json 2> $O/n2.err || { echo "self-launched N=2 failed"; tail -20 $O/n2.err; exit 1; }
 echo "lines on stdout: $(grep -c '^{' $O/n2.json)"

@@ -7,7 +7,7 @@ mkdir -p $O
 for pt in ${POINTS:-8:-1:-1 8:0:512 8:-1:512 8:0:1024 4:-1:-1 4:0:256 4:0:512}; do
   IFS=: read n f k <<< "$pt"
   tag=n${n}_f${f}_k${k}
-  timeout -k 10 240 python bench.py --emulate-ranks $n --queue-fill $f --strong-coalesce $k --no-per-frame \
+  timeout -k 10 240 python bench.py --full --emulate-ranks $n --queue-fill $f --strong-coalesce $k --no-per-frame \
       --no-cpu-baseline --no-framed --no-fast-bvh --steps ${STEPS:-16} > $O/$tag.json 2> $O/$tag.err || { tail -5 $O/$tag.err; exit 1; }
   python3 -c "
 import json; r = json.loads(open('$O/$tag.json').read().strip().splitlines()[-1]); s = r['strong_scaling']

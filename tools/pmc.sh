@@ -3,7 +3,7 @@
 # Usage: TAG=x ARGS="bench args" bash tools/pmc.sh "GROUP1" "GROUP2" ...   (a GROUP is a space-separated list)
 set -u
 TAG=${TAG:-x}
-ARGS=${ARGS:---steps 1 --warmup 1 --frames-per-step 16 --no-cpu-baseline}
+ARGS=${ARGS:---full --steps 1 --warmup 1 --frames-per-step 16 --no-cpu-baseline}
 OUT=$PWD/gpurun_out/prof
 mkdir -p "$OUT"
 export TMPDIR=/tmp

@@ -4,7 +4,7 @@
 #   TAG=r02d bash tools/pmc_deep.sh ; python tools/pmc_table.py gpurun_out/prof/deep*_r02d
 set -u
 TAG=${TAG:-deep}
-ARGS=${BENCH_ARGS:---steps 4 --warmup 1 --no-cpu-baseline --no-framed}
+ARGS=${BENCH_ARGS:---full --steps 4 --warmup 1 --no-cpu-baseline --no-framed}
 OUT=$PWD/gpurun_out/prof
 mkdir -p "$OUT"
 export TMPDIR=/tmp

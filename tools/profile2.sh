@@ -2,7 +2,7 @@
 # rocprofv3 kernel stats + two PMC groups for one bench configuration.  Usage: TAG=x ARGS="..." profile2.sh
 set -u
 TAG=${TAG:-x}
-ARGS=${ARGS:---steps 1 --warmup 1 --frames-per-step 16 --no-cpu-baseline}
+ARGS=${ARGS:---full --steps 1 --warmup 1 --frames-per-step 16 --no-cpu-baseline}
 OUT=$PWD/gpurun_out/prof
 mkdir -p "$OUT"
 export TMPDIR=/tmp

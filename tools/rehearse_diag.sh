@@ -1,7 +1,7 @@
 set -u
 mkdir -p gpurun_out/dist
 export HALOGEN_BENCH_DEVICE=0
-ARGS="--config C3 --width 640 --height 360 --steps 1 --warmup 1 --no-cpu-baseline --frames-per-step 8"
+ARGS="--full --config C3 --width 640 --height 360 --steps 1 --warmup 1 --no-cpu-baseline --frames-per-step 8"
 for K in stream regen; do
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --dist-backend gloo $ARGS --kernel $K --save-image gpurun_out/dist/n2_$K.npy > gpurun_out/dist/n2_$K.json 2> gpurun_out/dist/n2_$K.err || exit 1
   timeout -k 10 300 python bench.py $ARGS --kernel $K --frames-per-step 16 --save-image gpurun_out/dist/n1_$K.npy > gpurun_out/dist/n1_$K.json 2> gpurun_out/dist/n1_$K.err || exit 1
