@@ -171,8 +171,10 @@ __device__ __forceinline__ int32_t mat_priority(const HgKernelParams& kp, uint32
 // ---------------------------------------------------------------------------------------------------
 // 1/x, correctly rounded (the reference's `1 / det`, `1 / dir` in IEEE fp32).  With HG_FAST_RCP the hardware
 // reciprocal (<= 1 ulp) is refined by one FMA Newton step, correctly rounded for every x whose exponent keeps x
-// and 1/x normal (checked for all 2^32 inputs by hg_selftest, tests/test_gpu_selftest.py); zeros, denormals,
-// huge values, infinities and NaNs take the IEEE division.
+// and 1/x normal (the same three operations are checked for all 2^32 inputs by hg_selftest, tests/test_gpu_selftest.py);
+// zeros, denormals, huge values, infinities and NaNs take the IEEE division.  This function itself, fallback exponents
+// (0, 1, 253-255) included, is run against float32(1) / x by tests/test_gpu_device_units.py
+// (test_gpu_rcp_exact_is_ieee_division, through csrc/hg_devprobe.hip).
 __device__ __forceinline__ float rcp_exact(float x) {
 #if HG_FAST_RCP
     const uint32_t ex = (__float_as_uint(x) >> 23) & 0xFFu;
@@ -248,13 +250,13 @@ __device__ __forceinline__ uint2 leaf_range(const HgKernelParams& kp, uint32_t r
 __device__ __forceinline__ float ray_aabb(f3 A, f3 B, f3 o, f3 inv) {  // :244-259
     f3 t1 = (A - o) * inv;
     f3 t2 = (B - o) * inv;
-    float tMin = fminf(t1.x, t2.x);
-    float tMax = fmaxf(t1.x, t2.x);
-    tMin = fmaxf(tMin, fminf(t1.y, t2.y));
-    tMax = fminf(tMax, fmaxf(t1.y, t2.y));
-    tMin = fmaxf(tMin, fminf(t1.z, t2.z));
-    tMax = fminf(tMax, fmaxf(t1.z, t2.z));
-    return tMax > fmaxf(0.0f, tMin) ? tMin : HG_INF;
+    float tMin = hg_fminf(t1.x, t2.x);
+    float tMax = hg_fmaxf(t1.x, t2.x);
+    tMin = hg_fmaxf(tMin, hg_fminf(t1.y, t2.y));
+    tMax = hg_fminf(tMax, hg_fmaxf(t1.y, t2.y));
+    tMin = hg_fmaxf(tMin, hg_fminf(t1.z, t2.z));
+    tMax = hg_fminf(tMax, hg_fmaxf(t1.z, t2.z));
+    return tMax > hg_fmaxf(0.0f, tMin) ? tMin : HG_INF;
 }
 
 // A child-pair record (hg_runtime.hip, BLAS pass 2): both children's boxes and refs in 64 B, 56 of them used:
@@ -1000,7 +1002,7 @@ __device__ __forceinline__ float schlick_adjusted(float n1, float n2, f3 nrm, f3
 }
 
 __device__ __forceinline__ f3 refract_tir(f3 inc, f3 nrm, float n1, float n2, bool& tir) {  // :557-572
-    float ct = fminf(dot(-inc, nrm), 1.0f);
+    float ct = hg_fminf(dot(-inc, nrm), 1.0f);
     float st = __builtin_sqrtf(1.0f - ct * ct);
     float n12 = n1 / n2;
     if (n12 * st > 1.0f) {
@@ -1176,7 +1178,7 @@ __device__ f3 trace_ray(const HgKernelParams& kp, Sampler& smp, MediumStack& ms,
             acc_rough += mt.emis_rough.w * thr.x;  // float3 -> float truncation (:911)
             const float rr = smp.get1(ID_RR);
             smp.offset += BOUNCE_INC;
-            const float contribution = fmaxf(fmaxf(thr.x, thr.y), thr.z);
+            const float contribution = hg_fmaxf(hg_fmaxf(thr.x, thr.y), thr.z);
             if (rr > contribution) break;
             thr = thr * rcp_exact(contribution);
         } else {

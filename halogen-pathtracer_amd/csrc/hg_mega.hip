@@ -552,7 +552,7 @@ __global__ __launch_bounds__(HG_STREAM_LB, HG_MEGA_WAVES) void hg_trace_regen_ke
                 acc_rough += mt.emis_rough.w * thr.x;
                 const float rr = smp.get1(ID_RR);
                 smp.offset += BOUNCE_INC;
-                const float contribution = fmaxf(fmaxf(thr.x, thr.y), thr.z);
+                const float contribution = hg_fmaxf(hg_fmaxf(thr.x, thr.y), thr.z);
                 if (!(rr > contribution)) {
                     thr = thr * rcp_exact(contribution);
                     bounce += 1u << 24;
@@ -1400,7 +1400,7 @@ __global__ __launch_bounds__(HG_STREAM_LB, HG_STREAM_WAVES) void hg_trace_stream
                     acc_rough += mt.emis_rough.w * thr.x;
                     const float rr = smp.get1(ID_RR);
                     smp.offset += BOUNCE_INC;
-                    const float contribution = fmaxf(fmaxf(thr.x, thr.y), thr.z);
+                    const float contribution = hg_fmaxf(hg_fmaxf(thr.x, thr.y), thr.z);
                     if (!(rr > contribution)) {
                         thr = thr * rcp_exact(contribution);
                         bounce += 1u << 24;

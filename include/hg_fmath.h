@@ -13,6 +13,13 @@
  * of IEEE-754 binary32 +, -, *, /, sqrt and exact integer/bit operations only.  Both the gfx950 kernel
  * (hipcc) and the oracle (gcc) compile it with `-ffp-contract=off` and without fast-math, so each call
  * produces identical bits on both sides (gfx950 keeps fp32 denormals by default; x86 SSE does too).
+ * tests/test_gpu_device_units.py evaluates the device compilation of every function next to the host one.
+ *
+ * Domain: every float, NaN and +-Inf included, except that hg_sinf / hg_cosf / hg_tanf / hg_sincosf are defined
+ * for |x| <= 1e9 (and for NaN and +-Inf) only.  hg_reduce_quadrant_ converts |x| * 4/pi to int, which C leaves
+ * undefined once the product passes INT_MAX (|x| above about 1.69e9: x86 returns INT_MIN, gfx950 saturates), so
+ * the two sides may differ there.  Nothing on the path comes near it: the arguments are u * 2 pi, acos results and
+ * radians(fov).
  *
  * The polynomial kernels are the classic Cephes single-precision ones (S. L. Moshier, "Methods and
  * Programs for Mathematical Functions"); their coefficients are published constants.  Accuracy vs libm
@@ -26,7 +33,7 @@
  *   exp      (HalgoenCompute.compute:812)           -> hg_expf
  *   radians  (HalogenDefines.hlsl:12, Random:305)   -> x * HG_DEG2RAD (DXC folds radians() to one fmul)
  *   round    (HalgoenCompute.compute:941)           -> hg_roundf (round-half-to-even, DXIL Round_ne)
- *   min/max  (HalgoenCompute.compute:249-258)       -> fminf/fmaxf (IEEE minNum/maxNum, DXIL FMin/FMax)
+ *   min/max  (HalgoenCompute.compute:249-258)       -> hg_fminf / hg_fmaxf (DXIL FMin/FMax; -0 < +0, NaN dropped)
  *   normalize                                       -> v * (1/sqrt(dot(v,v)))   (see hg_rnorm)
  *   dot(a,b)                                        -> (a.x*b.x + a.y*b.y) + a.z*b.z, no FMA
  *   lerp(a,b,s)                                     -> a + s*(b - a)
@@ -63,6 +70,35 @@ HG_FN float hg_u2f(uint32_t u) {
     union { float f; uint32_t u; } c;
     c.u = u;
     return c.f;
+}
+
+/* min / max (HLSL min / max -> DXIL FMin / FMax), defined as IEEE 754-2019 minimumNumber / maximumNumber: a NaN operand
+ * is dropped (NaN only when both are), and -0 orders below +0.  The C library's fminf / fmaxf pin neither the zero's
+ * sign (glibc's x86 fmaxf(+0, -0) is -0, fmaxf(-0, +0) is +0) nor, in the standard, which zero a target returns, so the
+ * operation is spelled out here in compare / select form.  gfx950's v_min_f32 / v_max_f32 implement exactly this
+ * definition, so the device compilation uses the instruction (ray_aabb is the traversal's inner loop);
+ * tests/test_gpu_device_units.py compares the two forms on every pairing of zeros, denormals, infinities and NaNs. */
+HG_FN float hg_fminf(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fminf(a, b);
+#else
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a < b) return a;
+    if (b < a) return b;
+    return hg_u2f(hg_f2u(a) | hg_f2u(b)); /* equal: the same bits, or zeros of either sign -> -0 if one is */
+#endif
+}
+HG_FN float hg_fmaxf(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fmaxf(a, b);
+#else
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a > b) return a;
+    if (b > a) return b;
+    return hg_u2f(hg_f2u(a) & hg_f2u(b)); /* equal: the same bits, or zeros of either sign -> +0 if one is */
+#endif
 }
 
 /* x * 2^n for integer n, exact where the result is representable, IEEE-rounded into the denormal range.

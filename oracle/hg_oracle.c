@@ -348,13 +348,13 @@ typedef struct {
 static float ray_aabb(f3 A, f3 B, const ray_t* r) {
     f3 t1 = mul3(sub3(A, r->o), r->d);
     f3 t2 = mul3(sub3(B, r->o), r->d);
-    float tMin = fminf(t1.x, t2.x);
-    float tMax = fmaxf(t1.x, t2.x);
-    tMin = fmaxf(tMin, fminf(t1.y, t2.y));
-    tMax = fminf(tMax, fmaxf(t1.y, t2.y));
-    tMin = fmaxf(tMin, fminf(t1.z, t2.z));
-    tMax = fminf(tMax, fmaxf(t1.z, t2.z));
-    return tMax > fmaxf(0.0f, tMin) ? tMin : HG_INF;
+    float tMin = hg_fminf(t1.x, t2.x);
+    float tMax = hg_fmaxf(t1.x, t2.x);
+    tMin = hg_fmaxf(tMin, hg_fminf(t1.y, t2.y));
+    tMax = hg_fminf(tMax, hg_fmaxf(t1.y, t2.y));
+    tMin = hg_fmaxf(tMin, hg_fminf(t1.z, t2.z));
+    tMax = hg_fminf(tMax, hg_fmaxf(t1.z, t2.z));
+    return tMax > hg_fmaxf(0.0f, tMin) ? tMin : HG_INF;
 }
 
 /* sphere_intersection, :266-303 */
@@ -602,7 +602,7 @@ static float schlick_adjusted(float n1, float n2, f3 normal, f3 incident, float 
 }
 
 static f3 refract_tir(f3 incident, f3 normal, float n1, float n2, int* tir) { /* :557-572 */
-    float cos_theta = fminf(dot3(neg3(incident), normal), 1.0f);
+    float cos_theta = hg_fminf(dot3(neg3(incident), normal), 1.0f);
     float sin_theta = __builtin_sqrtf(1.0f - cos_theta * cos_theta);
     float n12 = n1 / n2;
     if (n12 * sin_theta > 1.0f) {
@@ -779,7 +779,7 @@ static f3 trace_ray(tstate* t, ray_t ray) {
             accRough += mat->roughness * thr.x; /* float3 -> float truncation (:911) */
             float rr = float_sobol(t, ID_RR);
             t->dim_offset += BOUNCE_INC;
-            float contribution = fmaxf(fmaxf(thr.x, thr.y), thr.z);
+            float contribution = hg_fmaxf(hg_fmaxf(thr.x, thr.y), thr.z);
             if (rr > contribution) break;
             thr = muls(thr, 1.0f / contribution);
         } else {
@@ -1197,5 +1197,99 @@ void hgo_fmath(int32_t fn, const float* x, float* y, int64_t n) {
             default: r = hg_asinf(v); break;
         }
         y[i] = r;
+    }
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Batch forms of the per-stage functions for tests/test_gpu_device_units.py: each calls the static functions
+ * above once per element, so the device building blocks (csrc/hg_devprobe.hip) can be compared on millions
+ * of inputs.  The element layouts are the probe's (hg_devprobe.hip).
+ * ---------------------------------------------------------------------------------------------- */
+void hgo_pcg_hash_batch(const uint32_t* in, uint32_t* out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) out[i] = hgo_pcg_hash(in[i]);
+}
+
+/* in: (frame, pixelID, dim_offset, id) per element; get1: 1 float, get2: 2 floats per element */
+void hgo_sampler_batch(const uint32_t* in, float* get1, float* get2, int64_t n) {
+    tstate t;
+    memset(&t, 0, sizeof t);
+    for (int64_t i = 0; i < n; i++) {
+        t.frame = in[4 * i];
+        t.pixelID = in[4 * i + 1];
+        t.dim_offset = in[4 * i + 2];
+        if (get1) get1[i] = float_sobol(&t, in[4 * i + 3]);
+        if (get2) float2_sobol(&t, in[4 * i + 3], get2 + 2 * i);
+    }
+}
+
+/* fn 12 hg_fminf(a, b), 13 hg_fmaxf(a, b) of the host compilation; in: 2 floats per element */
+void hgo_fmath2(int32_t fn, const float* x, float* y, int64_t n) {
+    for (int64_t i = 0; i < n; i++) y[i] = fn == 12 ? hg_fminf(x[2 * i], x[2 * i + 1]) : hg_fmaxf(x[2 * i], x[2 * i + 1]);
+}
+
+/* in: (A, B, o, inv_d), 12 floats per element */
+void hgo_aabb_batch(const float* in, float* out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) {
+        const float* e = in + 12 * i;
+        ray_t r = {v3(e[6], e[7], e[8]), v3(e[9], e[10], e[11])};
+        out[i] = ray_aabb(v3(e[0], e[1], e[2]), v3(e[3], e[4], e[5]), &r);
+    }
+}
+
+/* 1 / d as scene_isect_spheres and scene_isect_meshes invert a direction (the C division of this build) */
+void hgo_rcp_batch(const float* in, float* out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) out[i] = 1.0f / in[i];
+}
+
+/* The mesh loop's triangle test and accept rule (HC:404-420, scene_isect_meshes above): rays = (o, d, closest), 7
+ * floats per element; out = (accepted, rayT bits, u bits, v bits, orientation > 0), 5 words per element (the last four
+ * are triangle_intersection's, whether accepted or not). */
+void hgo_tri_accept_batch(const float* rays, const HalogenTriangle* tris, uint32_t* out, int64_t n) {
+    const float eps = 0.0001f;
+    for (int64_t i = 0; i < n; i++) {
+        const float* e = rays + 7 * i;
+        ray_t ray = {v3(e[0], e[1], e[2]), v3(e[3], e[4], e[5])};
+        const float closest = e[6];
+        tri_isect is = triangle_intersection(&ray, &tris[i]);
+        uint32_t* o = out + 5 * i;
+        o[0] = (is.rayT > eps && is.rayT < closest) ? 1u : 0u;
+        o[1] = hg_f2u(is.rayT);
+        o[2] = hg_f2u(is.u);
+        o[3] = hg_f2u(is.v);
+        o[4] = is.orientation > 0.0f ? 1u : 0u;
+    }
+}
+
+/* The sphere loop (HC:357-376, scene_isect_spheres above) over one sphere: in = (o, d, closest, far, centre, radius,
+ * cornerA, -, cornerB, -), 20 floats per element; out = (0 | (orientation < 0) << 31, or 0xFFFFFFFF when the sphere is
+ * not accepted; closest distance bits afterwards), 2 words per element. */
+void hgo_sphere_accept_batch(const float* in, uint32_t* out, int64_t n) {
+    hgo_scene sc;
+    hg_params p;
+    tstate t;
+    HalogenSphere s;
+    memset(&sc, 0, sizeof sc);
+    memset(&p, 0, sizeof p);
+    memset(&t, 0, sizeof t);
+    memset(&s, 0, sizeof s);
+    sc.spheres = &s;
+    sc.n_spheres = 1;
+    p.bufferCounts.x = 1.0f;
+    t.sc = &sc;
+    t.p = &p;
+    for (int64_t i = 0; i < n; i++) {
+        const float* e = in + 20 * i;
+        ray_t ray = {v3(e[0], e[1], e[2]), v3(e[3], e[4], e[5])};
+        hit_t h;
+        memset(&h, 0, sizeof h);
+        h.rayT = e[6];
+        p.viewParameters.w = e[7];
+        s.center.x = e[8]; s.center.y = e[9]; s.center.z = e[10];
+        s.radius = e[11];
+        s.boundingCornerA.x = e[12]; s.boundingCornerA.y = e[13]; s.boundingCornerA.z = e[14];
+        s.boundingCornerB.x = e[16]; s.boundingCornerB.y = e[17]; s.boundingCornerB.z = e[18];
+        scene_isect_spheres(&t, &ray, &h);
+        out[2 * i] = h.orientation != 0.0f ? (h.orientation < 0.0f ? 0x80000000u : 0u) : 0xFFFFFFFFu;
+        out[2 * i + 1] = hg_f2u(h.rayT);
     }
 }

@@ -80,6 +80,14 @@ void hgo_cube_sample(const hgo_scene* scene, const float dir[3], int32_t level, 
 /* Seamless cube filtering: the adjacent face's texel for texel (i, j) one step outside face f (out: face, i, j). */
 void hgo_cube_adjacent(int32_t f, int32_t i, int32_t j, int32_t size, int32_t out[3]);
 void hgo_fmath(int32_t fn, const float* x, float* y, int64_t n);
+void hgo_fmath2(int32_t fn, const float* x, float* y, int64_t n); /* 12 hg_fminf, 13 hg_fmaxf; x: pairs */
+/* Batch forms for tests/test_gpu_device_units.py (element layouts: hg_oracle.c, csrc/hg_devprobe.hip) */
+void hgo_pcg_hash_batch(const uint32_t* in, uint32_t* out, int64_t n);
+void hgo_sampler_batch(const uint32_t* in, float* get1, float* get2, int64_t n);
+void hgo_aabb_batch(const float* in, float* out, int64_t n);
+void hgo_rcp_batch(const float* in, float* out, int64_t n);
+void hgo_tri_accept_batch(const float* rays, const HalogenTriangle* tris, uint32_t* out, int64_t n);
+void hgo_sphere_accept_batch(const float* in, uint32_t* out, int64_t n);
 
 #ifdef __cplusplus
 }

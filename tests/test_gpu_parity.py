@@ -94,12 +94,19 @@ def test_gpu_frame_splits_and_tiling(gpu, kernel):
         assert_bitwise(merged, ref, f"{n_ranks} tiles")
 
 
+FULL_SIZE_BANDS = [("C3", (536, 540)), ("C3", (300, 303)), ("C2", (536, 540)), ("C2", (760, 763)), ("C5", (400, 403)),
+                   ("C5", (500, 503))]
+# (config, rows, first FrameCount, kernel): every band on every kernel from FrameCount 1, and two bands at the timed
+# headline's last frame numbers (FrameCount 1,279 and 1,280) on the kernels the headline runs
+FULL_SIZE_CASES = [pytest.param(c, r, 1, k, id=f"{c}-rows{i}-{k}") for i, (c, r) in enumerate(FULL_SIZE_BANDS)
+                   for k in sorted(KERNELS)]
+FULL_SIZE_CASES += [pytest.param(c, r, 1279, k, id=f"{c}-rows{r[0]}-frame1279-{k}")
+                    for c, r in (("C3", (536, 540)), ("C2", (760, 763))) for k in ("auto", "stream")]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("kernel", sorted(KERNELS))
-@pytest.mark.parametrize("cfg_name,rows", [("C3", (536, 540)), ("C3", (300, 303)), ("C2", (536, 540)),
-                                           ("C2", (760, 763)), ("C5", (400, 403)),
-                                           ("C5", (500, 503))])
-def test_gpu_full_size_rows_match_oracle(gpu, cfg_name, rows, kernel):
+@pytest.mark.parametrize("cfg_name,rows,first_frame,kernel", FULL_SIZE_CASES)
+def test_gpu_full_size_rows_match_oracle(gpu, cfg_name, rows, first_frame, kernel):
     """BASELINE-sized configs (1080p; C3 with the full 871,200-triangle dragon): a band of rows traced by the
     oracle must equal the same rows of the GPU image, bit for bit.  The bands cross the box (C2 760-763 also the
     ceiling light, seen directly by ~10 % of its pixels): more than half of their paths hit geometry, and some of
@@ -109,17 +116,62 @@ def test_gpu_full_size_rows_match_oracle(gpu, cfg_name, rows, kernel):
     s = rp.clamp_settings(settings)
     packed = cases._scene(cfg.scene, 10)
     cube = settings.environmentCubemap if s["UseEnvironmentCubemap"] else None
-    params = rp.make_params(s, cfg.camera(), 1, len(packed.spheres), len(packed.meshes), cube is not None)
+    params = rp.make_params(s, cfg.camera(), first_frame, len(packed.spheres), len(packed.meshes), cube is not None)
     frames = 2
     img, _ = gpu_render(packed, params, frames, True, cube, kernel=kernel)
     W = cfg.width
     y0, y1 = rows
     ref, rcnt = hg_oracle.render(packed, params, frames, True, cubemap=cube, pix_range=(y0 * W, y1 * W))
     assert_bitwise(img[y0:y1], ref[y0:y1], f"{cfg_name} rows {rows}")
-    assert np.all(img[..., 3] == 1.0) and np.isfinite(img).all()
+    # alpha: 1 after a progressive render from FrameCount 1; from a later first FrameCount the blend weights (1 / FrameCount)
+    # of the two frames leave the cleared target's 0 mostly in place, the same value in every pixel (the oracle's)
+    alpha = np.float32(1.0) if first_frame == 1 else ref[y0, 0, 3]
+    assert 0 < alpha <= 1 and np.all(img[..., 3] == alpha) and np.isfinite(img).all()
     lit = (ref[y0:y1, :, :3].max(-1) > 0).mean()
     assert rcnt["hits"] > 0.5 * rcnt["paths"] and lit > 0.03, (
         f"band {rows}: {rcnt['hits']} hits for {rcnt['paths']} paths, {lit:.3f} lit: not a parity check")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kernel", sorted(KERNELS))
+@pytest.mark.parametrize("name", ["c1_64", "glass_64x36", "dragon1_64x36"])
+def test_gpu_headline_frame_numbers_match_oracle(gpu, name, kernel):
+    """FrameCount 1,279 and 1,280, the last Sobol indices the timed headline traces (no committed image goes above 16),
+    against the live oracle."""
+    packed, params, cube, _, acc = cases.setup(name, first_frame=1279)
+    assert params.frameCount == 1279
+    img, cnt = gpu_render(packed, params, 2, acc, cube, kernel=kernel)
+    ref, rcnt = hg_oracle.render(packed, params, 2, acc, cubemap=cube)
+    assert_bitwise(img, ref, f"{name} FrameCount 1279-1280")
+    for k in ("rays", "tri_tests", "aabb_tests", "hits"):
+        assert cnt[k] == rcnt[k], (k, cnt[k], rcnt[k])
+
+
+_frame_range_ref = []
+
+
+def frame_range_reference():
+    """dragon10_64x36 for 64 frames from FrameCount 1 by the oracle, computed once."""
+    if not _frame_range_ref:
+        packed, params, cube, _, acc = cases.setup("dragon10_64x36")
+        ref, rcnt = hg_oracle.render(packed, params, 64, acc, cubemap=cube)
+        ref.setflags(write=False)
+        _frame_range_ref.append((ref, rcnt))
+    return _frame_range_ref[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("splits", [None, [1, 63]], ids=["one_launch", "split_1_63"])
+@pytest.mark.parametrize("kernel", ["auto", "stream"])
+def test_gpu_frame_range_matches_oracle(gpu, kernel, splits):
+    """A whole image over FrameCount 1..64 (the 871k-triangle dragon), in one launch and as 1 + 63 frames: the image and
+    the four work counters equal the live oracle's."""
+    packed, params, cube, _, acc = cases.setup("dragon10_64x36")
+    ref, rcnt = frame_range_reference()
+    img, cnt = gpu_render(packed, params, 64, acc, cube, kernel=kernel, splits=splits)
+    assert_bitwise(img, ref, f"dragon10_64x36 frames 1-64 {kernel} {splits}")
+    for k in ("rays", "tri_tests", "aabb_tests", "hits"):
+        assert cnt[k] == rcnt[k], (k, cnt[k], rcnt[k])
 
 
 @pytest.mark.gpu
