@@ -88,6 +88,35 @@ public static class HalogenNative
     public const int HG_DISPLAY_RGBA32F = 0, HG_DISPLAY_RGBA16F = 1, HG_DISPLAY_R11G11B10F = 2;
     public const int HG_SELFTEST_RCP = 1, HG_SELFTEST_BUILD = 2, HG_BUILD_CHECK_EXEC = 1, HG_BUILD_NO_REGEN_ITEMS = 2;
     public const int HG_COMM_ID_BYTES = 128, HG_COMM_RCCL = 1, HG_COMM_PEER = 2;
+    // ray queries (hg_trace_rays): hg_ray_hit.kind and the query mode
+    public const int HG_HIT_NONE = 0, HG_HIT_MESH = 1, HG_HIT_SPHERE = 2;
+    public const int HG_RAYS_CLOSEST = 0, HG_RAYS_ANY = 1;
+
+    // hg_ray (32 B): a unit-length direction; t_max = float.PositiveInfinity for an unbounded ray; flags reserved (0)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HgRay
+    {
+        public Vector3 origin;
+        public float t_max;
+        public Vector3 direction;
+        public uint flags;
+    }
+
+    // hg_ray_hit (48 B): kind HG_HIT_*; object = index of the mesh / sphere in the uploaded arrays; primitive = index
+    // in the uploaded triangle array; a miss has kind HG_HIT_NONE and t = +inf
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HgRayHit
+    {
+        public float t;
+        public uint kind;
+        public uint @object;
+        public uint primitive;
+        public float u, v;
+        public uint material;
+        public float orientation;
+        public Vector3 normal;
+        public uint reserved;
+    }
 
     [DllImport(Lib)] public static extern int hg_abi_version();
     [DllImport(Lib)] public static extern int hg_create(int device, out IntPtr ctx);
@@ -123,6 +152,13 @@ public static class HalogenNative
     [DllImport(Lib)] public static extern int hg_reset_counters(IntPtr ctx);
     [DllImport(Lib)] public static extern int hg_set_option(IntPtr ctx, int option, int value);
     [DllImport(Lib)] public static extern long hg_selftest(IntPtr ctx, int test, out long tested);
+    // Ray queries over the uploaded scene (picking, autofocus, visibility): synchronous, host arrays or device pointers
+    [DllImport(Lib)] public static extern int hg_trace_rays(IntPtr ctx, HgRay[] rays, long n, int mode,
+        [Out] HgRayHit[] hits);
+    [DllImport(Lib)] public static extern int hg_trace_rays_device(IntPtr ctx, IntPtr dRays, long n, int mode,
+        IntPtr dHits);
+    [DllImport(Lib)] public static extern int hg_camera_rays(IntPtr ctx, ref HgParams p, int frameCount,
+        int[] pixelsXY, long n, [Out] HgRay[] rays);
     [DllImport(Lib)] public static extern long hg_build_blas(float[] vertices, int nVertices, int[] indices, int nTris,
         float[] rootMin, float[] rootMax, int maxHierarchyDepth, [Out] BVHEntry[] outNodes, long maxNodes);
     [DllImport(Lib)] public static extern long hg_build_blas_mt(float[] vertices, int nVertices, int[] indices,

@@ -47,6 +47,9 @@ struct hg_ctx {
     DevBuf acc;
 
     DevBuf spill;  // traversal stack entries beyond the LDS part, per thread, of launches on the context stream
+    // Ray queries (hg_trace_rays, hg_camera_rays): device staging of one launch's input records (rays / pixels) and
+    // output records (hits / rays) of the host-pointer forms; grown on demand, reused, freed by hg_destroy
+    DevBuf query_in, query_out;
     // Trace pipeline (hg_render): the regenerating / streaming kernels trace each launch chunk on one of HG_TRACE_LANES
     // side streams, in turn, into that stream's own frame-colour buffer; the chunk's in-order blend into the accumulator
     // runs on `stream`.  So a chunk's tail overlaps the next chunk's trace, and everything else on `stream` (readback,

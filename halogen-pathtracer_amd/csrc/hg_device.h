@@ -752,6 +752,106 @@ __device__ __forceinline__ Hit intersect(const HgKernelParams& kp, const Ray& ra
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Ray queries (hg_query.hip): get_ray_intersection for a caller's ray, handing out which primitive was hit.
+// isect_meshes_best is isect_meshes statement for statement (a copy, so that the megakernels' instantiations of
+// isect_meshes stay what they are; change both together) with two differences: the accepted hit's u, v, triangle and
+// mesh are returned beside Hit, and the work counters are gone.  kAny (occlusion): the lane leaves the mesh cursor at
+// the first triangle that would make the closest query report a mesh hit, i.e. one accepted below seed - 1e-4 (:452);
+// accepted triangles inside that 1e-4 band only lower best_t, as in the closest query, so up to the exit both
+// traversals are the same and `found` equals "the closest query reports a mesh hit".
+// ---------------------------------------------------------------------------------------------------
+struct MeshBest {
+    float u, v;
+    uint32_t tri;   // global triangle index | (orientation < 0) << 31, HG_NONE: no mesh hit
+    uint32_t mesh;
+};
+
+template <bool kAny, class Stk>
+__device__ bool isect_meshes_best(const HgKernelParams& kp, const Ray& ray, Hit& h, MeshBest& mb, const Stk& stk) {
+    const float eps = 0.0001f;
+    float best_t = h.t;  // the seed: the sphere hit (:381), else the ray's t_max
+    float best_u = 0.0f, best_v = 0.0f;
+    uint32_t best_tri = HG_NONE;
+    uint32_t best_mesh = 0;
+    uint32_t culled = 0;
+    bool found = false;
+    const f3 winv = mk(rcp_exact(ray.d.x), rcp_exact(ray.d.y), rcp_exact(ray.d.z));
+    const uint64_t live = mesh_live_mask(kp, ray.o, winv, best_t, culled);
+    const uint32_t nm = uint32_t(kp.n_meshes);
+    uint32_t mi = next_live_mesh(live, 0u, nm);
+    bool active = mi < nm;
+    f3 lo = mk(0, 0, 0), ld = mk(0, 0, 0), inv = mk(0, 0, 0);
+    uint32_t node = HG_NONE, sp = 0;
+    if (active) mesh_local_ray(kp, ray, mi, lo, ld, inv, node);
+    while (__any(active)) {
+        const uint64_t act_mask = wave_ballot(active);
+        const uint32_t dt = kp.descent_t;
+        for (uint64_t dm = act_mask & wave_ballot(int32_t(node) >= 0);
+             dm != 0ull && (uint32_t(__builtin_popcountll(dm)) > dt || dm == act_mask);
+             dm = act_mask & wave_ballot(int32_t(node) >= 0)) {
+            if (active && int32_t(node) >= 0) {
+                const NodePair np = node_pair(kp, node);
+                float dA, dB;
+                pair_dist(np, lo, inv, dA, dB);
+                const uint32_t refA = pair_ref_a(np), refB = pair_ref_b(np);
+                const bool bFirst = dB < dA;  // :430-444
+                const uint32_t nearRef = bFirst ? refB : refA, farRef = bFirst ? refA : refB;
+                const bool nearOk = (bFirst ? dB : dA) < best_t, farOk = (bFirst ? dA : dB) < best_t;
+                if (nearOk) {
+                    if (farOk) stk.push(sp, farRef);
+                    node = nearRef;
+                } else if (farOk) {
+                    node = farRef;
+                } else {
+                    node = sp > 0 ? stk.pop(sp) : HG_NONE;
+                }
+            }
+        }
+        if (active && node != HG_NONE && (node & HG_LEAF_BIT)) {  // a leaf: its triangles in order (:404-420)
+            const uint2 leaf = leaf_range(kp, node);
+            const uint32_t end = leaf.x + leaf.y;
+            for (uint32_t ti = leaf.x; ti < end; ++ti) {
+                float4 a, b;
+                float cz;
+                tri_load(kp, ti, a, b, cz);
+                float t, U, V;
+                bool front;
+                if (tri_accept(lo, ld, a, b, cz, best_t, t, U, V, front)) {
+                    best_t = t;
+                    best_u = U;
+                    best_v = V;
+                    best_tri = ti | (front ? 0u : 0x80000000u);
+                    best_mesh = mi;
+                    if constexpr (kAny) {
+                        if (t < (h.t - eps)) {
+                            found = true;
+                            break;
+                        }
+                    }
+                }
+            }
+            node = sp > 0 ? stk.pop(sp) : HG_NONE;
+        }
+        if constexpr (kAny) {
+            if (found) active = false;  // the wave loop's __any(active) ends once every lane has its answer
+        }
+        if (active && node == HG_NONE) {  // this mesh is done: the lane's next live mesh
+            mi = next_live_mesh(live, mi + 1u, nm);
+            if (mi < nm) mesh_local_ray(kp, ray, mi, lo, ld, inv, node);
+            else active = false;
+        }
+    }
+    mb = MeshBest{best_u, best_v, best_tri, best_mesh};
+    if constexpr (kAny) return found;
+    // :452-471
+    if (best_t < (h.t - eps) && best_t < kp.far_) {
+        resolve_mesh(kp, ray, best_t, best_u, best_v, best_tri, best_mesh, h);
+        return true;
+    }
+    return false;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Resumable get_ray_intersection (:474-485) for the streaming kernel: the same spheres / exact mesh cull /
 // per-lane mesh cursor / while-while traversal as intersect(), with its state in a struct so a lane can stop
 // between steps (other lanes shade) and resume.  Same visit order, same counters, same result.

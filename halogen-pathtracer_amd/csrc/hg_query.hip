@@ -1,0 +1,121 @@
+// hg_query.hip — ray queries over the uploaded scene (hg_trace_rays, hg_trace_rays_device, hg_camera_rays): the
+// reference's get_ray_intersection (HalgoenCompute.compute:474-485) for a caller's rays, with no shading, no sampler and
+// no accumulation, and the camera rays a frame traces (get_ray, :996-1013) handed out as such rays.
+//
+// A translation unit of its own: the megakernels of hg_mega.hip compile to what they compile to without it.
+#include <hip/hip_runtime.h>
+
+#include "halogen_abi.h"
+#include "hg_device.h"
+
+using namespace hgd;
+
+static_assert(sizeof(hg_ray) == 32 && sizeof(hg_ray_hit) == 48, "the kernels move these records as float4");
+
+#ifndef HG_QUERY_WAVES
+#define HG_QUERY_WAVES 8  // waves/SIMD target: the traversal alone needs 59 (closest) / 48 (any) VGPRs, no scratch
+#endif
+constexpr int kQueryBlock = 256;  // four waves per workgroup, the lockstep kernel's [depth][thread] LDS stack
+
+// One lane per ray, 64 consecutive rays per wave.  Record i is two float4: (origin, t_max), (direction, flags); result
+// i is three: (t, kind, object, primitive), (u, v, material, orientation), (normal, 0).  Lanes past n in the last wave
+// stay in the wave with a ray that can hit nothing (t_max = -inf: no triangle is accepted below it and every node
+// test fails) and write nothing: the traversal's wave loop ballots over all 64 lanes.
+template <bool kAny>
+__global__ __launch_bounds__(kQueryBlock, HG_QUERY_WAVES) void hg_query_kernel(const HgKernelParams kp,
+                                                                               const float4* __restrict__ rays,
+                                                                               float4* __restrict__ hits, uint32_t n) {
+    const uint32_t i = blockIdx.x * uint32_t(kQueryBlock) + threadIdx.x;
+    const bool live = i < n;
+    float4 ro = make_float4(0.0f, 0.0f, 0.0f, -HG_INF), rd = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+    if (live) {
+        ro = rays[2u * i];
+        rd = rays[2u * i + 1u];
+    }
+    const MegaStack stk{threadIdx.x, uint32_t(kQueryBlock), kp.spill + i, kp.spill_stride};
+    const Ray ray{mk(ro.x, ro.y, ro.z), mk(rd.x, rd.y, rd.z)};
+    Hit h;
+    h.t = ro.w;  // the closest distance is seeded with t_max (+inf: the path tracer's get_ray_intersection)
+    h.orient = 0.0f;
+    h.pos = mk(0, 0, 0);
+    h.n = mk(0, 0, 0);
+    h.mat = 0;
+    const uint32_t sph = isect_spheres(kp, ray, h.t);
+    MeshBest mb{0.0f, 0.0f, HG_NONE, 0u};
+    uint32_t kind = HG_HIT_NONE, object = 0u, prim = 0u;
+    if constexpr (kAny) {
+        // a sphere hit alone makes the closest query report a hit; such a lane brings a ray that hits no mesh
+        if (sph != HG_NONE) h.t = -HG_INF;
+        const bool mesh = isect_meshes_best<true>(kp, ray, h, mb, stk);
+        kind = sph != HG_NONE ? uint32_t(HG_HIT_SPHERE) : mesh ? uint32_t(HG_HIT_MESH) : uint32_t(HG_HIT_NONE);
+        h.t = kind != HG_HIT_NONE ? 0.0f : HG_INF;
+        mb.u = mb.v = 0.0f;
+    } else {
+        if (isect_meshes_best<false>(kp, ray, h, mb, stk)) {
+            kind = HG_HIT_MESH;
+            object = mb.mesh;
+            prim = mb.tri & 0x7FFFFFFFu;
+        } else if (sph != HG_NONE) {
+            resolve_sphere(kp, ray, sph, h);
+            kind = HG_HIT_SPHERE;
+            object = sph & 0x7FFFFFFFu;
+            mb.u = mb.v = 0.0f;  // (a mesh hit inside the 1e-4 band behind the sphere is not the answer)
+        } else {
+            h.t = HG_INF;  // a miss: +inf whatever t_max was, everything else 0
+            mb.u = mb.v = 0.0f;
+        }
+    }
+    if (live) {
+        hits[3u * i] = make_float4(h.t, __uint_as_float(kind), __uint_as_float(object), __uint_as_float(prim));
+        hits[3u * i + 1u] = make_float4(mb.u, mb.v, __uint_as_float(h.mat), h.orient);
+        hits[3u * i + 2u] = make_float4(h.n.x, h.n.y, h.n.z, 0.0f);
+    }
+}
+
+// The first camera ray (sample 0) frame `frame` traces for each listed pixel: camera_ray seeded as hg_trace_kernel
+// seeds it (hg_mega.hip), ndc of :1023-1033.
+__global__ __launch_bounds__(kQueryBlock) void hg_camera_rays_kernel(const HgKernelParams kp, uint32_t frame,
+                                                                     const int2* __restrict__ pixels,
+                                                                     float4* __restrict__ rays, uint32_t n) {
+    const uint32_t i = blockIdx.x * uint32_t(kQueryBlock) + threadIdx.x;
+    if (i >= n) return;
+    const int2 p = pixels[i];
+    const uint32_t px = uint32_t(p.x), py = uint32_t(p.y);
+    const float ndcx = (float(px) / kp.W) * 2.0f - 1.0f;
+    const float ndcy = (float(py) / kp.H) * 2.0f - 1.0f;
+    const Sampler smp{frame, pcg_hash(px + py * kp.Wu), 0u};
+    const Ray r = camera_ray(kp, smp, ndcx, ndcy);
+    rays[2u * i] = make_float4(r.o.x, r.o.y, r.o.z, HG_INF);
+    rays[2u * i + 1u] = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
+}
+
+// threads of a query launch over n rays (the spill buffer has one column per thread: kp.spill_stride)
+uint32_t hg_query_threads(uint32_t n) {
+    return (n + uint32_t(kQueryBlock) - 1u) / uint32_t(kQueryBlock) * uint32_t(kQueryBlock);
+}
+// LDS stack entries per lane of the query kernel; deeper entries go to kp.spill
+uint32_t hg_query_lds_stack() { return HG_MEGA_LDS_STACK; }
+
+hipError_t hg_launch_query(const HgKernelParams& kp, const void* rays, void* hits, uint32_t n, bool any,
+                           hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint32_t grid = hg_query_threads(n) / uint32_t(kQueryBlock);
+    const size_t lds = size_t(kp.stack_depth < HG_MEGA_LDS_STACK ? kp.stack_depth : HG_MEGA_LDS_STACK) *
+                       size_t(kQueryBlock) * sizeof(uint32_t);
+    if (any)
+        hipLaunchKernelGGL((hg_query_kernel<true>), dim3(grid), dim3(kQueryBlock), lds, stream, kp,
+                           static_cast<const float4*>(rays), static_cast<float4*>(hits), n);
+    else
+        hipLaunchKernelGGL((hg_query_kernel<false>), dim3(grid), dim3(kQueryBlock), lds, stream, kp,
+                           static_cast<const float4*>(rays), static_cast<float4*>(hits), n);
+    return hipGetLastError();
+}
+
+hipError_t hg_launch_camera_rays(const HgKernelParams& kp, uint32_t frame, const void* pixels, void* rays, uint32_t n,
+                                 hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint32_t grid = hg_query_threads(n) / uint32_t(kQueryBlock);
+    hipLaunchKernelGGL(hg_camera_rays_kernel, dim3(grid), dim3(kQueryBlock), 0, stream, kp, frame,
+                       static_cast<const int2*>(pixels), static_cast<float4*>(rays), n);
+    return hipGetLastError();
+}

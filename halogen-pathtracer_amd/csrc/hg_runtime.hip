@@ -518,7 +518,7 @@ void hg_destroy(hg_ctx* c) {
     for (hg_ctx::TraceLane& L : c->lanes)
         if (L.stream) (void)hipStreamSynchronize(L.stream);
     for (DevBuf* b : {&c->spheres, &c->meshes, &c->materials, &c->nodes, &c->leaves, &c->tris, &c->normals, &c->cube,
-                      &c->acc, &c->counters_dev, &c->spill, &c->lost})
+                      &c->acc, &c->counters_dev, &c->spill, &c->lost, &c->query_in, &c->query_out})
         release(*b);
     auto destroy_lanes = [c] {
         for (hg_ctx::TraceLane& L : c->lanes) {
@@ -1236,6 +1236,26 @@ void note_call(hg_ctx* c) {
     c->calls++;
 }
 
+// The camera part of a launch's parameter block (everything camera_ray reads, hg_device.h) from the uniforms
+void set_camera(HgKernelParams& kp, const hg_params& p) {
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 4; ++k) kp.cam[r * 4 + k] = p.camLocalToWorld.m[k * 4 + r];
+    kp.W = p.screenParameters.x;
+    kp.H = p.screenParameters.y;
+    kp.Wu = uint32_t(p.screenParameters.x);
+    kp.Hu = uint32_t(p.screenParameters.y);
+    kp.vw = p.viewParameters.x;
+    kp.vh = p.viewParameters.y;
+    kp.near_ = p.viewParameters.z;
+    kp.far_ = p.viewParameters.w;
+    // tan(radians(focalConeAngle)) * ViewParameters.z (:998), once per launch with the shared spec
+    kp.focal_disc_radius = hg_tanf(p.focalConeAngle * HG_DEG2RAD) * p.viewParameters.z;
+    kp.psx = (p.viewParameters.x * 2.0f) / p.screenParameters.x;  // get_ray_jitter :986
+    kp.psy = (p.viewParameters.y * 2.0f) / p.screenParameters.y;
+    kp.filter_radius = p.filterRadius;
+    kp.focal_dist = p.focalPlaneDistance;
+}
+
 // One launch of n_frames frames from FrameCount = params.frameCount (which it advances when accumulating)
 int render_now(hg_ctx* c, int32_t n_frames, int32_t accumulate) {
     if (!c->has_scene) return fail(c, HG_E_NOSCENE, "hg_upload_scene not called");
@@ -1253,22 +1273,8 @@ int render_now(hg_ctx* c, int32_t n_frames, int32_t accumulate) {
     if (int rc = set_device(c)) return rc;
 
     HgKernelParams kp{};
-    for (int r = 0; r < 3; ++r)
-        for (int k = 0; k < 4; ++k) kp.cam[r * 4 + k] = p.camLocalToWorld.m[k * 4 + r];
-    kp.W = p.screenParameters.x;
-    kp.H = p.screenParameters.y;
-    kp.Wu = uint32_t(p.screenParameters.x);
+    set_camera(kp, p);
     kp.Hu = uint32_t(c->H);
-    kp.vw = p.viewParameters.x;
-    kp.vh = p.viewParameters.y;
-    kp.near_ = p.viewParameters.z;
-    kp.far_ = p.viewParameters.w;
-    // tan(radians(focalConeAngle)) * ViewParameters.z (:998), once per launch with the shared spec
-    kp.focal_disc_radius = hg_tanf(p.focalConeAngle * HG_DEG2RAD) * p.viewParameters.z;
-    kp.psx = (p.viewParameters.x * 2.0f) / p.screenParameters.x;  // get_ray_jitter :986
-    kp.psy = (p.viewParameters.y * 2.0f) / p.screenParameters.y;
-    kp.filter_radius = p.filterRadius;
-    kp.focal_dist = p.focalPlaneDistance;
     kp.spp = p.samplesPerPixel;
     kp.max_bounces = p.maxBounces;
     kp.max_diff = p.maxDiffuseBounces;
@@ -2086,6 +2092,153 @@ int hg_set_option(hg_ctx* c, int32_t option, int32_t value) {
         default:
             return fail(c, HG_E_INVALID, "unknown option %d", option);
     }
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Ray queries (hg_trace_rays, hg_trace_rays_device, hg_camera_rays; kernels in hg_query.hip)
+// ---------------------------------------------------------------------------------------------------------------------
+uint32_t hg_query_threads(uint32_t n);
+uint32_t hg_query_lds_stack();
+hipError_t hg_launch_query(const HgKernelParams& kp, const void* rays, void* hits, uint32_t n, bool any,
+                           hipStream_t stream);
+hipError_t hg_launch_camera_rays(const HgKernelParams& kp, uint32_t frame, const void* pixels, void* rays, uint32_t n,
+                                 hipStream_t stream);
+
+namespace {
+
+constexpr int64_t kQueryChunk = int64_t(1) << 20;  // records per launch (and per staging buffer)
+
+// What every entry point but hg_render does first, as far as hg_synchronize takes it: the held frames launched, the
+// render server stopped, every stream of the context idle
+int query_begin(hg_ctx* c) {
+    if (int rc = hg_ctx_flush(c)) return rc;
+    if (int rc = set_device(c)) return rc;
+    return quiesce(c);
+}
+
+// The parameter block of a query launch of `threads` threads: the uploaded scene (all of it: no bufferCounts, no
+// tiling), far = +inf, the lockstep kernel's descent threshold; nothing of the target, the uniforms or the counters
+int query_params(hg_ctx* c, uint32_t threads, HgKernelParams& kp) {
+    kp = HgKernelParams{};
+    kp.far_ = HG_INF;
+    kp.n_spheres = c->n_spheres;
+    kp.n_meshes = c->n_meshes;
+    kp.stack_depth = c->stack_depth;
+    const bool deep_blas = c->stack_depth > HG_DESCENT_DEEP + 2;
+    kp.descent_t = c->descent_t >= 0 ? uint32_t(c->descent_t) : deep_blas ? uint32_t(HG_DESCENT_T) : 0u;
+    kp.spheres = static_cast<const float4*>(c->spheres.p);
+    kp.meshes = static_cast<const HgDevMesh*>(c->meshes.p);
+    kp.materials = static_cast<const float4*>(c->materials.p);
+    kp.nodes = static_cast<const float4*>(c->nodes.p);
+    kp.leaves = static_cast<const uint2*>(c->leaves.p);
+    kp.tris = static_cast<const float*>(c->tris.p);
+    kp.normals = static_cast<const float4*>(c->normals.p);
+    kp.spill_stride = threads;
+    const uint32_t lds_part = hg_query_lds_stack();
+    if (kp.stack_depth > lds_part) {  // one spill column per thread (the context is idle: the buffer may move)
+        if (int rc = ensure(c, c->spill, size_t(threads) * (kp.stack_depth - lds_part) * sizeof(uint32_t))) return rc;
+        kp.spill = static_cast<uint32_t*>(c->spill.p);
+    }
+    return HG_OK;
+}
+
+int query_args(hg_ctx* c, const void* in, int64_t n, int32_t mode, const void* out) {
+    if (n < 0) return fail(c, HG_E_INVALID, "negative ray count");
+    if (mode != HG_RAYS_CLOSEST && mode != HG_RAYS_ANY) return fail(c, HG_E_INVALID, "unknown ray query mode %d", mode);
+    if (!in || !out) return fail(c, HG_E_INVALID, "null array with a non-zero ray count");
+    if (!c->has_scene) return fail(c, HG_E_NOSCENE, "hg_upload_scene not called");
+    return HG_OK;
+}
+
+// n rays at device pointers, in launches of at most kQueryChunk; the context is idle (query_begin) and the caller waits
+// for the stream
+int query_launch(hg_ctx* c, const void* d_rays, int64_t n, int32_t mode, void* d_hits) {
+    HgKernelParams kp;
+    if (int rc = query_params(c, hg_query_threads(uint32_t(std::min(n, kQueryChunk))), kp)) return rc;
+    for (int64_t at = 0; at < n; at += kQueryChunk) {
+        const uint32_t m = uint32_t(std::min(n - at, kQueryChunk));
+        HG_HIP(c, hg_launch_query(kp, static_cast<const hg_ray*>(d_rays) + at, static_cast<hg_ray_hit*>(d_hits) + at, m,
+                                  mode == HG_RAYS_ANY, c->stream));
+    }
+    return HG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hg_trace_rays_device(hg_ctx* c, const void* d_rays, int64_t n, int32_t mode, void* d_hits) {
+    if (!c) return HG_E_INVALID;
+    if (n == 0) return HG_OK;
+    if (int rc = query_args(c, d_rays, n, mode, d_hits)) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_rays) | reinterpret_cast<uintptr_t>(d_hits)) & 15u)
+        return fail(c, HG_E_INVALID, "device ray / hit arrays must be 16-byte aligned");
+    if (int rc = query_begin(c)) return rc;
+    if (int rc = query_launch(c, d_rays, n, mode, d_hits)) return rc;
+    HG_HIP(c, hipStreamSynchronize(c->stream));
+    return HG_OK;
+}
+
+int hg_trace_rays(hg_ctx* c, const hg_ray* rays, int64_t n, int32_t mode, hg_ray_hit* hits) {
+    if (!c) return HG_E_INVALID;
+    if (n == 0) return HG_OK;
+    if (int rc = query_args(c, rays, n, mode, hits)) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        const hg_ray& r = rays[i];
+        if (!(std::isfinite(r.origin.x) && std::isfinite(r.origin.y) && std::isfinite(r.origin.z)))
+            return fail(c, HG_E_INVALID, "ray %lld: origin is not finite", (long long)i);
+        if (!(std::isfinite(r.direction.x) && std::isfinite(r.direction.y) && std::isfinite(r.direction.z)))
+            return fail(c, HG_E_INVALID, "ray %lld: direction is not finite", (long long)i);
+        if (r.direction.x == 0.0f && r.direction.y == 0.0f && r.direction.z == 0.0f)
+            return fail(c, HG_E_INVALID, "ray %lld: zero direction", (long long)i);
+        if (std::isnan(r.t_max)) return fail(c, HG_E_INVALID, "ray %lld: t_max is NaN", (long long)i);
+    }
+    if (int rc = query_begin(c)) return rc;
+    const size_t cap = size_t(std::min(n, kQueryChunk));
+    if (int rc = ensure(c, c->query_in, cap * sizeof(hg_ray))) return rc;
+    if (int rc = ensure(c, c->query_out, cap * sizeof(hg_ray_hit))) return rc;
+    for (int64_t at = 0; at < n; at += kQueryChunk) {  // in stream order: a chunk's copies and launch reuse the staging
+        const size_t m = size_t(std::min(n - at, kQueryChunk));
+        HG_HIP(c, hipMemcpyAsync(c->query_in.p, rays + at, m * sizeof(hg_ray), hipMemcpyHostToDevice, c->stream));
+        if (int rc = query_launch(c, c->query_in.p, int64_t(m), mode, c->query_out.p)) return rc;
+        HG_HIP(c, hipMemcpyAsync(hits + at, c->query_out.p, m * sizeof(hg_ray_hit), hipMemcpyDeviceToHost, c->stream));
+    }
+    HG_HIP(c, hipStreamSynchronize(c->stream));
+    return HG_OK;
+}
+
+int hg_camera_rays(hg_ctx* c, const hg_params* p, int32_t frame_count, const int32_t* pixels_xy, int64_t n,
+                   hg_ray* rays) {
+    if (!c) return HG_E_INVALID;
+    if (n == 0) return HG_OK;
+    if (n < 0) return fail(c, HG_E_INVALID, "negative pixel count");
+    if (!p || !pixels_xy || !rays) return fail(c, HG_E_INVALID, "null params or array with a non-zero pixel count");
+    const float Wf = p->screenParameters.x, Hf = p->screenParameters.y;
+    if (!(Wf >= 1.0f && Hf >= 1.0f && Wf <= 65536.0f && Hf <= 65536.0f))
+        return fail(c, HG_E_INVALID, "screenParameters (%g,%g) out of range", Wf, Hf);
+    const int32_t W = int32_t(Wf), H = int32_t(Hf);
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t x = pixels_xy[2 * i], y = pixels_xy[2 * i + 1];
+        if (x < 0 || x >= W || y < 0 || y >= H)
+            return fail(c, HG_E_INVALID, "pixel %lld: (%d,%d) outside the %dx%d screen", (long long)i, x, y, W, H);
+    }
+    if (int rc = query_begin(c)) return rc;
+    HgKernelParams kp{};
+    set_camera(kp, *p);
+    const size_t cap = size_t(std::min(n, kQueryChunk));
+    if (int rc = ensure(c, c->query_in, cap * 2 * sizeof(int32_t))) return rc;
+    if (int rc = ensure(c, c->query_out, cap * sizeof(hg_ray))) return rc;
+    for (int64_t at = 0; at < n; at += kQueryChunk) {
+        const size_t m = size_t(std::min(n - at, kQueryChunk));
+        HG_HIP(c, hipMemcpyAsync(c->query_in.p, pixels_xy + 2 * at, m * 2 * sizeof(int32_t), hipMemcpyHostToDevice,
+                                 c->stream));
+        HG_HIP(c, hg_launch_camera_rays(kp, uint32_t(frame_count), c->query_in.p, c->query_out.p, uint32_t(m), c->stream));
+        HG_HIP(c, hipMemcpyAsync(rays + at, c->query_out.p, m * sizeof(hg_ray), hipMemcpyDeviceToHost, c->stream));
+    }
+    HG_HIP(c, hipStreamSynchronize(c->stream));
+    return HG_OK;
 }
 
 }  // extern "C"

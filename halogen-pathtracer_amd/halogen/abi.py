@@ -94,8 +94,28 @@ class HgCounters(C.Structure):
                 for name, v in ((name, getattr(self, name)) for name, _ in self._fields_)}
 
 
+class HgRay(C.Structure):  # hg_ray, 32 B: a unit-length direction; t_max = +inf for an unbounded ray
+    _fields_ = [("origin", Vec3), ("t_max", C.c_float), ("direction", Vec3), ("flags", C.c_uint32)]
+
+
+class HgRayHit(C.Structure):  # hg_ray_hit, 48 B
+    _fields_ = [("t", C.c_float), ("kind", C.c_uint32), ("object", C.c_uint32), ("primitive", C.c_uint32),
+                ("u", C.c_float), ("v", C.c_float), ("material", C.c_uint32), ("orientation", C.c_float),
+                ("normal", Vec3), ("reserved", C.c_uint32)]
+
+
+# numpy views of the two records (Context.trace_rays / camera_rays): the same bytes as the ctypes mirrors
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("direction", np.float32, 3),
+                      ("flags", np.uint32)])
+RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("kind", np.uint32), ("object", np.uint32), ("primitive", np.uint32),
+                          ("u", np.float32), ("v", np.float32), ("material", np.uint32), ("orientation", np.float32),
+                          ("normal", np.float32, 3), ("reserved", np.uint32)])
+HG_HIT_NONE, HG_HIT_MESH, HG_HIT_SPHERE = 0, 1, 2
+HG_RAYS_CLOSEST, HG_RAYS_ANY = 0, 1
+RAY_MODES = {"closest": HG_RAYS_CLOSEST, "any": HG_RAYS_ANY}
+
 HG_OK = 0
-HG_KERNEL_MEGA, HG_KERNEL_WAVEFRONT, HG_KERNEL_MEGA_REGEN, HG_KERNEL_MEGA_STREAM, HG_KERNEL_MEGA_POOL = 0, 1, 2, 3, 4
+HG_KERNEL_MEGA,HG_KERNEL_WAVEFRONT, HG_KERNEL_MEGA_REGEN, HG_KERNEL_MEGA_STREAM, HG_KERNEL_MEGA_POOL = 0, 1, 2, 3, 4
 HG_KERNEL_AUTO = 5
 HG_OPT_KERNEL, HG_OPT_BLOCK, HG_OPT_COUNTERS, HG_OPT_TIMING, HG_OPT_REFILL, HG_OPT_FRAME_SPLIT = 1, 2, 3, 4, 5, 6
 HG_OPT_DESCENT_T = 7
@@ -125,7 +145,7 @@ EXPORTS = [
     "hg_set_params", "hg_resize", "hg_set_tiling", "hg_clear_accumulation", "hg_render", "hg_synchronize",
     "hg_readback", "hg_readback_begin", "hg_readback_end", "hg_readback_begin_format", "hg_readback_end_data",
     "hg_pack_display", "hg_set_accumulation", "hg_copy_tiles_device", "hg_local_tile_count", "hg_get_counters", "hg_reset_counters",
-    "hg_set_option", "hg_selftest", "hg_build_blas", "hg_build_blas_mt", "hg_build_blas_sah", "hg_unity_bounds", "hg_pack_triangles",
+    "hg_set_option", "hg_selftest", "hg_trace_rays", "hg_trace_rays_device", "hg_camera_rays", "hg_build_blas", "hg_build_blas_mt", "hg_build_blas_sah", "hg_unity_bounds", "hg_pack_triangles",
     "hg_comm_unique_id", "hg_comm_init_rank", "hg_comm_init_all", "hg_comm_gather", "hg_comm_synchronize",
     "hg_comm_readback", "hg_comm_readback_begin", "hg_comm_readback_end", "hg_comm_set_timeout_ms", "hg_comm_transport", "hg_comm_last_error", "hg_comm_destroy",
     "hg_comm_assemble_host",
@@ -177,6 +197,9 @@ def lib() -> C.CDLL:
         "hg_reset_counters": (C.c_int, [P]),
         "hg_set_option": (C.c_int, [P, i32, i32]),
         "hg_selftest": (i64, [P, i32, C.POINTER(i64)]),
+        "hg_trace_rays": (C.c_int, [P, P, i64, i32, P]),
+        "hg_trace_rays_device": (C.c_int, [P, P, i64, i32, P]),
+        "hg_camera_rays": (C.c_int, [P, C.POINTER(HgParams), i32, P, i64, P]),
         "hg_build_blas": (i64, [P, i32, P, i32, f32p, f32p, i32, P, i64]),
         "hg_build_blas_mt": (i64, [P, i32, P, i32, f32p, f32p, i32, P, i64, i32]),
         "hg_build_blas_sah": (i64, [P, i32, P, i32, i32, i32, P, i64]),
@@ -353,6 +376,48 @@ class Context:
 
     def set_option(self, option: int, value: int) -> None:
         self._check(lib().hg_set_option(self._h, option, value), "hg_set_option")
+
+    # --- ray queries (hg_trace_rays, hg_trace_rays_device, hg_camera_rays) --------------------------------------------
+    def trace_rays(self, rays, mode="closest"):
+        """Closest-hit ("closest") or occlusion ("any") query of n rays over the uploaded scene.
+
+        rays on the host: an (n, 8) float32 array (origin xyz, t_max, unit direction xyz, 0) or a RAY_DTYPE array;
+        returns a RAY_HIT_DTYPE array of n hits.  rays as a contiguous (n, 8) float32 torch tensor on the context's
+        device: traced in place through the device entry point (no copy); returns an (n, 12) float32 tensor on that
+        device, rows laid out as hg_ray_hit (view it as int32 for kind / object / primitive / material).  (A process
+        that uses both imports torch before it creates its first Context, so that both share one HIP runtime.)"""
+        m = RAY_MODES[mode] if isinstance(mode, str) else int(mode)
+        if hasattr(rays, "data_ptr") and not isinstance(rays, np.ndarray):
+            import torch
+
+            if not (rays.is_cuda and rays.device.index == self.device and rays.dtype == torch.float32 and
+                    rays.dim() == 2 and rays.shape[1] == 8 and rays.is_contiguous()):
+                raise ValueError(f"device rays must be a contiguous (n, 8) float32 tensor on cuda:{self.device}")
+            hits = torch.empty((rays.shape[0], 12), dtype=torch.float32, device=rays.device)
+            torch.cuda.current_stream(rays.device).synchronize()  # the rays are complete before the call
+            self._check(lib().hg_trace_rays_device(self._h, C.c_void_p(rays.data_ptr()), rays.shape[0], m,
+                                                   C.c_void_p(hits.data_ptr())), "hg_trace_rays_device")
+            return hits
+        a = np.asarray(rays)
+        if a.dtype != RAY_DTYPE:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 8:
+                raise ValueError(f"rays must be (n, 8) float32 or a RAY_DTYPE array, got {a.shape}")
+        a = np.ascontiguousarray(a).reshape(-1) if a.dtype == RAY_DTYPE else a
+        n = a.shape[0]
+        hits = np.zeros(n, dtype=RAY_HIT_DTYPE)
+        self._check(lib().hg_trace_rays(self._h, _ptr(a) if n else None, n, m, _ptr(hits) if n else None),
+                    "hg_trace_rays")
+        return hits
+
+    def camera_rays(self, params: HgParams, frame_count: int, pixels) -> np.ndarray:
+        """The first camera ray (sample 0) frame `frame_count` traces for each (x, y) of `pixels` ((n, 2) integers),
+        as a RAY_DTYPE array with t_max = +inf (hg_camera_rays; `params` is explicit, the context's are not read)."""
+        px = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
+        rays = np.zeros(px.shape[0], dtype=RAY_DTYPE)
+        self._check(lib().hg_camera_rays(self._h, C.byref(params), int(frame_count), _ptr(px), px.shape[0], _ptr(rays)),
+                    "hg_camera_rays")
+        return rays
 
     def selftest(self, test: int = HG_SELFTEST_RCP) -> tuple[int, int]:
         """(mismatches, inputs tested) of a device arithmetic self-test."""

@@ -155,6 +155,7 @@ class HalogenRenderPass:
         self._prior_pose = None
         self._prior_resolution = None
         self._scene_counts = (0, 0)
+        self._last_scene, self._last_camera = None, None  # of the last Execute (pick / autofocus default to them)
         self._cubemap_uploaded = False
         # hg_upload_scene_gen's geometry generation: bumped whenever the scene's meshes (cache token, triangle and node
         # counts, in order) differ from the last upload's, so a camera move's re-upload compares only the small arrays
@@ -219,6 +220,7 @@ class HalogenRenderPass:
         if self.FrameCount > 1 and not self.s["Accumulate"]:
             self.ClearAccumulation()
         self._prior_pose = pose
+        self._last_scene, self._last_camera = scene, camera
         if self.ObjectBuffersDirty:
             self.UpdateObjectBuffers(scene)
             self.ObjectBuffersDirty = False
@@ -286,6 +288,41 @@ class HalogenRenderPass:
         self.ctx.set_accumulation(image, frame_count)
         self.FrameCount = int(frame_count)
         self.AccumulationBufferDirty = False
+
+    # ---- ray queries (not in the reference, which asks the engine's physics) ---------------------------------------
+    def pick(self, x: int, y: int, scene=None, camera: Camera | None = None):
+        """What is under pixel (x, y): the pinhole centre ray of the pixel (the current uniforms with filterRadius = 0
+        and focalConeAngle = 0, so neither jitter nor lens moves it) through hg_camera_rays and hg_trace_rays.
+        Returns (kind, scene object, t, hit record) — kind "mesh" / "sphere", the object of the scene last executed (or
+        of `scene`; its index when neither is known), t the distance along the ray — or None on a miss.  `camera`
+        defaults to the camera of the last Execute."""
+        camera = camera if camera is not None else self._last_camera
+        scene = scene if scene is not None else self._last_scene
+        if camera is None:
+            raise abi.HalogenError("pick: no camera (Execute first, or pass one)")
+        p = make_params(self.s, camera, self.FrameCount, *self._scene_counts, self.s["UseEnvironmentCubemap"])
+        p.filterRadius = 0.0
+        p.focalConeAngle = 0.0
+        ray = self.ctx.camera_rays(p, self.FrameCount, [(int(x), int(y))])
+        hit = self.ctx.trace_rays(ray, "closest")[0]
+        if hit["kind"] == abi.HG_HIT_NONE:
+            return None
+        kind = "mesh" if hit["kind"] == abi.HG_HIT_MESH else "sphere"
+        objs = getattr(scene, "meshes" if kind == "mesh" else "spheres", None)
+        obj = objs[int(hit["object"])] if objs is not None and int(hit["object"]) < len(objs) else int(hit["object"])
+        return kind, obj, float(hit["t"]), hit
+
+    def autofocus(self, x: int, y: int, scene=None, camera: Camera | None = None):
+        """Focus on what is under pixel (x, y): sets the settings' FocalPlaneDistance to pick's t (get_ray measures the
+        focal distance along the ray, HC:996-1013) and restarts the accumulation.  A miss changes nothing.  Returns the
+        new distance or None."""
+        found = self.pick(x, y, scene, camera)
+        if found is None:
+            return None
+        self.settings.FocalPlaneDistance = found[2]
+        self.s = clamp_settings(self.settings)
+        self.ClearAccumulation()
+        return found[2]
 
     def getFrameCount(self) -> int:
         return self.FrameCount

@@ -401,6 +401,59 @@ enum { HG_BUILD_CHECK_EXEC = 1, HG_BUILD_NO_REGEN_ITEMS = 2 };
 int64_t hg_selftest(hg_ctx* ctx, int32_t test, int64_t* tested);
 
 /* ----------------------------------------------------------------------------------------------
+ * Ray queries over the uploaded scene (not in the reference, which gets picking and focus distances from the engine's
+ * physics): the library's own get_ray_intersection (HalgoenCompute.compute:474-485) for a caller's rays.
+ *
+ * HG_RAYS_CLOSEST answers a ray exactly as the path tracer's get_ray_intersection does: spheres first, then the meshes
+ * in buffer order, the same strict `<` tie rules and the same 1e-4 rules, with two changes that leave a ray with
+ * t_max = +inf bit-identical to the path tracer's: the closest distance is seeded with t_max instead of +inf (so a mesh
+ * hit is accepted only below seed - 1e-4f, as the reference accepts it against a sphere hit), and the far plane is
+ * +inf (the query reads neither hg_set_params nor hg_resize; it needs only an uploaded scene, else HG_E_NOSCENE, and
+ * answers for every uploaded sphere and mesh).  A hit has
+ *   t            the distance (the position is origin + direction * t),
+ *   kind         HG_HIT_MESH or HG_HIT_SPHERE,
+ *   object       the mesh's or sphere's index in the uploaded arrays,
+ *   primitive    the triangle's index in the uploaded triangle array (the mesh's triangleBufferOffset included); 0 for
+ *                a sphere,
+ *   u, v         the accepted barycentrics (0 for a sphere),
+ *   material     the material index,
+ *   orientation  +1 (front) or -1,
+ *   normal       the shading normal as the path tracer shades with it (world space, unit, times orientation).
+ * A miss has kind = HG_HIT_NONE and t = +inf, everything else 0.
+ * HG_RAYS_ANY (occlusion) defines only `kind`: HG_HIT_NONE exactly when the closest query reports none; which hit it
+ * names is unspecified.  A ray stops traversing at its first accepted primitive.
+ *
+ * Preconditions: directions are unit length (the sphere test assumes it; nothing is normalised), origins and
+ * directions are finite, t_max is not NaN.  The host-pointer form checks every ray before anything is launched and
+ * returns HG_E_INVALID (the error text names the first bad ray) for a non-finite origin or direction, a zero direction,
+ * a NaN t_max or an unknown mode; the device-pointer form has the same preconditions and does not check them.
+ * `flags` is reserved (0).  n == 0 returns HG_OK without touching the GPU; a NULL array with n > 0 is HG_E_INVALID.
+ *
+ * Ordering: like every entry point but hg_render, the three calls launch the held frames and stop a render server
+ * first and wait for the context's streams (as hg_synchronize does), run on the context stream, and return with the
+ * results complete.  They never touch the accumulation, FrameCount, hg_counters, the tiling or the options; a tiled
+ * context answers for the whole scene.  The device-pointer form is synchronous too: d_rays (n records of hg_ray) and
+ * d_hits (n of hg_ray_hit) are 16-byte aligned device memory on the context's device, and the caller must have
+ * finished producing d_rays before the call (the call does not wait for the caller's streams).
+ * -------------------------------------------------------------------------------------------- */
+typedef struct hg_ray { hg_vec3 origin; float t_max; hg_vec3 direction; uint32_t flags; } hg_ray;      /* 32 B */
+typedef struct hg_ray_hit {
+    float t; uint32_t kind; uint32_t object; uint32_t primitive;
+    float u, v; uint32_t material; float orientation;
+    hg_vec3 normal; uint32_t reserved;
+} hg_ray_hit;                                                                                          /* 48 B */
+enum { HG_HIT_NONE = 0, HG_HIT_MESH = 1, HG_HIT_SPHERE = 2 };
+enum { HG_RAYS_CLOSEST = 0, HG_RAYS_ANY = 1 };
+int hg_trace_rays(hg_ctx* ctx, const hg_ray* rays, int64_t n, int32_t mode, hg_ray_hit* hits);
+int hg_trace_rays_device(hg_ctx* ctx, const void* d_rays, int64_t n, int32_t mode, void* d_hits);
+/* The first camera ray (sample 0) that frame `frame_count` traces for each of the n listed pixels (pixels_xy = x0, y0,
+ * x1, y1, ...), written with t_max = +inf: get_ray (:996-1013) seeded as the render seeds it, jitter and thin lens
+ * included.  `params` is required and explicit (the context's own parameters are neither read nor changed); a pixel
+ * outside its screenParameters is HG_E_INVALID.  Needs no scene.  Host pointers. */
+int hg_camera_rays(hg_ctx* ctx, const hg_params* params, int32_t frame_count, const int32_t* pixels_xy, int64_t n,
+                   hg_ray* rays);
+
+/* ----------------------------------------------------------------------------------------------
  * Multi-GPU framebuffer gather (not in the reference, which is single-GPU).
  * Every rank renders the 8x8 tiles t % n_ranks == rank of the same image (hg_set_tiling) with its own context, on
  * its own GPU; the only exchange is one gather of the ranks' accumulated tiles to the root, which assembles the
