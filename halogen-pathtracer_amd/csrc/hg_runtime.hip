@@ -27,6 +27,8 @@
 #include "hg_interval.h"
 #include "hg_pack.h"
 #include "hg_host_pool.h"
+#include "hg_pair_guard.h"
+#include "hg_plan.h"
 
 hipError_t hg_launch_mega(const HgKernelParams& kp, int block, bool counters, hipStream_t stream);
 hipError_t hg_launch_mega_regen(const HgKernelParams& kp, int block, bool counters, hipStream_t stream);
@@ -44,7 +46,8 @@ int64_t hg_selftest_rcp_all(int64_t* tested);
 
 namespace {
 
-constexpr size_t kFrameColorCap = size_t(4) << 30;  // frame-parallel colour buffer cap (bytes)
+using EventPair = std::pair<hipEvent_t, hipEvent_t>;
+using EventGuard = HgPairGuard<EventPair>;  // a timing pair that goes back to free_events unless handed on
 constexpr uint32_t kMaxStack = 64;  // LDS stack entries per lane; BLAS depth must be <= kMaxStack - 2
 constexpr int kHostThreads = 16;    // host threads of hg_upload_scene's compare / repack (the GPU box's CPU share)
 
@@ -261,14 +264,16 @@ int drain_events(hg_ctx* c) {
     return HG_OK;
 }
 
-int event_pair(hg_ctx* c, std::pair<hipEvent_t, hipEvent_t>& ev) {
+int event_pair(hg_ctx* c, EventGuard& g) {
+    EventPair ev;
     if (!c->free_events.empty()) {
         ev = c->free_events.back();
         c->free_events.pop_back();
-        return HG_OK;
+    } else {
+        HG_HIP(c, hipEventCreate(&ev.first));
+        HG_HIP(c, hipEventCreate(&ev.second));
     }
-    HG_HIP(c, hipEventCreate(&ev.first));
-    HG_HIP(c, hipEventCreate(&ev.second));
+    g.hold(ev);
     return HG_OK;
 }
 
@@ -410,6 +415,31 @@ int ensure_quiet(hg_ctx* c, DevBuf& b, size_t bytes) {
     if (b.bytes >= std::max<size_t>(bytes, 16)) return HG_OK;
     if (int rc = quiesce(c)) return rc;
     return ensure(c, b, bytes);
+}
+
+// The cost order of a trace stream or of the render server (`o`: its tile_cost, tile_order, order_scratch and stream).
+// Two steps, because a call grows every trace stream's buffers before it queues its first chunk and sorts per chunk.
+// Grow: with `grow` (ensure, or ensure_quiet while traces may be in flight); the sort's scratch is zeroed once, when
+// allocated (each use leaves it zeroed).
+template <class Owner>
+int cost_order_ensure(hg_ctx* c, Owner& o, uint32_t tiles, int (*grow)(hg_ctx*, DevBuf&, size_t)) {
+    const size_t tb = size_t(tiles) * sizeof(uint32_t);
+    if (int rc = grow(c, o.tile_cost, 2 * tb)) return rc;
+    if (int rc = grow(c, o.tile_order, tb)) return rc;
+    const size_t osb = hg_order_scratch_bytes(tiles);
+    if (o.order_scratch.bytes >= osb) return HG_OK;
+    if (int rc = grow(c, o.order_scratch, osb)) return rc;
+    if (hipMemsetAsync(o.order_scratch.p, 0, o.order_scratch.bytes, o.stream) != hipSuccess)
+        return fail(c, HG_E_HIP, "hipMemsetAsync(order scratch) failed");
+    return HG_OK;
+}
+// Use: sort the recorded costs into the order (`sort`), or zero the costs before their first records
+template <class Owner>
+hipError_t cost_order_run(hg_ctx* c, Owner& o, uint32_t tiles, bool sort) {
+    unsigned long long* cost = static_cast<unsigned long long*>(o.tile_cost.p);
+    if (!sort) return hipMemsetAsync(cost, 0, size_t(tiles) * sizeof(unsigned long long), o.stream);
+    return hg_launch_order_tiles(cost, static_cast<uint32_t*>(o.tile_order.p), tiles, o.order_scratch.p,
+                                 static_cast<unsigned long long*>(c->counters_dev.p) + 18, o.stream);
 }
 
 int alloc_target(hg_ctx* c) {
@@ -985,20 +1015,15 @@ int server_start(hg_ctx* c, const HgKernelParams& kp_in, int32_t fc) {
         for (int k = 0; k < 4; ++k) S.host[k] = 0ull;
     }
     const uint32_t tiles = uint32_t(c->n_local_tiles);
-    const size_t per_frame = size_t(tiles) * 64u * sizeof(float4);
-    uint32_t ring = HG_SV_RING;
-    while (ring > 2u && size_t(ring) * per_frame > (size_t(2) << 30)) ring >>= 1;
     // waves per SIMD: HG_SV_WAVES, the kernel's occupancy (HALOGEN_SERVER_WAVES overrides, 1..HG_STREAM_WAVES, for A/B)
     static const uint32_t sv_waves = [] {
         const char* e = std::getenv("HALOGEN_SERVER_WAVES");
         const int v = e ? std::atoi(e) : 0;
         return uint32_t(v >= 1 && v <= HG_STREAM_WAVES ? v : HG_SV_WAVES);
     }();
-    const uint32_t slots = uint32_t(c->n_cu) * 4u * sv_waves;
-    const uint32_t grid = std::min(tiles, slots);
-    const uint32_t lds_part = HG_STREAM_LDS_STACK;
-    const size_t spill_bytes = kp_in.stack_depth > lds_part ? size_t(grid) * 64u * (kp_in.stack_depth - lds_part) * 4u : 0;
-    const size_t tb = size_t(tiles) * sizeof(uint32_t);
+    const HgServerPlan P = hg_plan_server(c->n_cu, tiles, kp_in.stack_depth, int(sv_waves));  // ring, grid, spill, divide
+    const uint32_t ring = P.ring, grid = P.grid;
+    const size_t per_frame = P.per_frame, spill_bytes = P.spill_bytes;
     // the last lifetime's gates and blends on the context stream read its ring and counts: everything below runs after
     // them (an event, no host wait) unless a buffer must move (then the context stream is drained first)
     if (S.ring.bytes < size_t(ring) * per_frame || S.done.bytes < size_t(ring) * 128u)
@@ -1008,45 +1033,34 @@ int server_start(hg_ctx* c, const HgKernelParams& kp_in, int32_t fc) {
     if (!rc) rc = ensure_uncached(c, S.ctl, HG_SV_CTL_BYTES);  // (polled by scalar loads: hg_mega.hip sv_sload)
     if (!rc && spill_bytes) rc = ensure(c, S.spill, spill_bytes);
     // the cost order only with HG_SV_COST_ORDER: the server's frames overlap, so no frame's end waits on its longest
-    // tiles, and raster order keeps a claim's consecutive tiles together (HG_SV_COST_ORDER in hg_layout.h)
+    // tiles, and raster order keeps a claim's consecutive tiles together (HG_SV_COST_ORDER in hg_tunables.h)
     const bool ordered = c->tile_order_on && HG_SV_COST_ORDER;
-    if (!rc && ordered) rc = ensure(c, S.tile_cost, 2 * tb);
-    if (!rc && ordered) rc = ensure(c, S.tile_order, tb);
-    const size_t osb = hg_order_scratch_bytes(tiles);
-    if (!rc && ordered && S.order_scratch.bytes < osb) {
-        rc = ensure(c, S.order_scratch, osb);
-        if (!rc && hipMemsetAsync(S.order_scratch.p, 0, S.order_scratch.bytes, S.stream) != hipSuccess)
-            rc = fail(c, HG_E_HIP, "hipMemsetAsync(server order scratch) failed");
-    }
+    if (!rc && ordered) rc = cost_order_ensure(c, S, tiles, ensure);
     if (rc) return rc;
     // The counts and heads are zeroed on the context stream: after the last lifetime's gates and blends, and before
     // this lifetime's gates, which are queued there too (zeroed on the server's stream instead, a new gate could read
     // the last lifetime's count of its ring slot before the zeroing and pass at once)
     HG_HIP(c, hipMemsetAsync(S.ctl.p, 0, HG_SV_CTL_BYTES, c->stream));
     HG_HIP(c, hipMemsetAsync(S.done.p, 0, size_t(ring) * 128u, c->stream));
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    if (int r = event_pair(c, ev)) return r;
-    HG_HIP(c, hipEventRecord(ev.first, c->stream));
-    HG_HIP(c, hipStreamWaitEvent(S.stream, ev.first, 0));
-    c->free_events.push_back(ev);
+    {
+        EventGuard ev(c->free_events);  // (given back at once: the wait holds what it needs of the event)
+        if (int r = event_pair(c, ev)) return r;
+        HG_HIP(c, hipEventRecord(ev.pair.first, c->stream));
+        HG_HIP(c, hipStreamWaitEvent(S.stream, ev.pair.first, 0));
+    }
     HgKernelParams kp = kp_in;
     kp.tile_order = nullptr;
     kp.tile_cost = nullptr;
-    if (ordered) {
+    if (ordered) {  // the cost order of the last lifetime's frames, or none yet
         kp.tile_cost = static_cast<unsigned long long*>(S.tile_cost.p);
-        if (S.tile_cost_valid) {  // the cost order of the last lifetime's frames
-            HG_HIP(c, hg_launch_order_tiles(kp.tile_cost, static_cast<uint32_t*>(S.tile_order.p), tiles, S.order_scratch.p,
-                                            static_cast<unsigned long long*>(c->counters_dev.p) + 18, S.stream));
-            kp.tile_order = static_cast<const uint32_t*>(S.tile_order.p);
-        } else {
-            HG_HIP(c, hipMemsetAsync(kp.tile_cost, 0, size_t(tiles) * sizeof(unsigned long long), S.stream));
-            S.tile_cost_valid = true;
-        }
+        HG_HIP(c, cost_order_run(c, S, tiles, S.tile_cost_valid));
+        if (S.tile_cost_valid) kp.tile_order = static_cast<const uint32_t*>(S.tile_order.p);
+        S.tile_cost_valid = true;
     }
     kp.frame_color = static_cast<float4*>(S.ring.p);
     kp.frames_done = static_cast<uint32_t*>(S.done.p);
     kp.queue = static_cast<uint32_t*>(S.ctl.p);
-    kp.resident_waves = slots;
+    kp.resident_waves = P.slots;
     kp.wave_units = 1;
     kp.spill = spill_bytes ? static_cast<uint32_t*>(S.spill.p) : nullptr;
     kp.spill_stride = grid * 64u;
@@ -1058,16 +1072,10 @@ int server_start(hg_ctx* c, const HgKernelParams& kp_in, int32_t fc) {
     HG_HIP(c, hipHostGetDevicePointer(&post, S.host, 0));
     kp.sv_post = static_cast<const unsigned long long*>(post);
     kp.sv_ring = ring;
-    kp.sv_frames_cap = std::min<uint32_t>(1u << 24, uint32_t((uint64_t(1) << 31) / std::max<uint32_t>(tiles, 1u)));
+    kp.sv_frames_cap = P.frames_cap;
     kp.sv_idle_ticks = uint32_t(std::min<uint64_t>(uint64_t(S.idle_us) * 100ull, 0xFFFFFFFFull));
-    if ((tiles & (tiles - 1u)) == 0u) {  // unit -> frame (hg_mega.hip sv_frame): a shift, or a multiply-high and a shift
-        kp.sv_div_magic = 0u;
-        kp.sv_div_shift = uint32_t(__builtin_ctz(tiles));
-    } else {
-        const uint32_t l = 31u - uint32_t(__builtin_clz(tiles));
-        kp.sv_div_magic = uint32_t(((uint64_t(1) << (32 + l)) + tiles - 1u) / tiles);
-        kp.sv_div_shift = l;
-    }
+    kp.sv_div_magic = P.div_magic;
+    kp.sv_div_shift = P.div_shift;
     // (the lost-frame word is not reset: a gate of the last lifetime may still report into it)
     __atomic_store_n(&S.host[HG_SV_HOST_POST], 0ull, __ATOMIC_SEQ_CST);
     __atomic_store_n(&S.host[HG_SV_HOST_CLOSING], 0ull, __ATOMIC_SEQ_CST);
@@ -1256,22 +1264,38 @@ void set_camera(HgKernelParams& kp, const hg_params& p) {
     kp.focal_dist = p.focalPlaneDistance;
 }
 
-// One launch of n_frames frames from FrameCount = params.frameCount (which it advances when accumulating)
-int render_now(hg_ctx* c, int32_t n_frames, int32_t accumulate) {
-    if (!c->has_scene) return fail(c, HG_E_NOSCENE, "hg_upload_scene not called");
-    if (!c->has_params) return fail(c, HG_E_INVALID, "hg_set_params not called");
-    if (c->W <= 0) return fail(c, HG_E_NOTARGET, "hg_resize not called");
-    if (n_frames < 0) return fail(c, HG_E_INVALID, "n_frames < 0");
-    const hg_params& p = c->params;
-    if (int32_t(p.screenParameters.x) != c->W || int32_t(p.screenParameters.y) != c->H)
-        return fail(c, HG_E_INVALID, "screenParameters (%g,%g) != target %dx%d", p.screenParameters.x,
-                    p.screenParameters.y, c->W, c->H);
-    const int32_t ns = int32_t(p.bufferCounts.x), nm = int32_t(p.bufferCounts.y);
-    if (ns < 0 || ns > c->n_spheres || nm < 0 || nm > c->n_meshes)
-        return fail(c, HG_E_INVALID, "bufferCounts (%d,%d) exceed uploaded (%d,%d)", ns, nm, c->n_spheres, c->n_meshes);
-    if (n_frames == 0) return HG_OK;
-    if (int rc = set_device(c)) return rc;
+// The scene part of a launch's parameter block: the uploaded arrays, the stack depth and the descent threshold
+void set_scene(HgKernelParams& kp, const hg_ctx* c, uint32_t descent_t) {
+    kp.stack_depth = c->stack_depth;
+    kp.descent_t = descent_t;
+    kp.spheres = static_cast<const float4*>(c->spheres.p);
+    kp.meshes = static_cast<const HgDevMesh*>(c->meshes.p);
+    kp.materials = static_cast<const float4*>(c->materials.p);
+    kp.nodes = static_cast<const float4*>(c->nodes.p);
+    kp.leaves = static_cast<const uint2*>(c->leaves.p);
+    kp.tris = static_cast<const float*>(c->tris.p);
+    kp.normals = static_cast<const float4*>(c->normals.p);
+}
 
+// The pixels of this rank's local tiles that lie in the image: f(accumulator slot, image pixel) (hg_tiling.h)
+template <class F>
+void for_local_pixels(const hg_ctx* c, F&& f) {
+    hg_for_local_pixels(uint32_t(c->W), uint32_t(c->H), uint32_t(c->n_local_tiles), uint32_t(c->rank),
+                        uint32_t(c->n_ranks), f);
+}
+
+// What the launch plan (hg_plan.h) reads of the context, its uniforms and the call
+HgPlanIn plan_input(const hg_ctx* c, int32_t n_frames) {
+    const hg_params& p = c->params;
+    return HgPlanIn{c->n_cu,        c->n_local_tiles, c->W,          c->H,          c->stack_depth,     c->n_meshes,
+                    c->kernel,      c->block,         c->frame_split, c->wave_units, c->queue_fill,      c->descent_t,
+                    c->tile_order_on, c->coalesce,    c->n_ranks,    p.halogenDebugMode, p.maxBounces, p.samplesPerPixel,
+                    n_frames};
+}
+
+// The parameter block of a render call planned as P; the chunks set their own frames and their trace stream's buffers
+HgKernelParams kernel_params(const hg_ctx* c, const HgCallPlan& P, int32_t n_frames, int32_t accumulate) {
+    const hg_params& p = c->params;
     HgKernelParams kp{};
     set_camera(kp, p);
     kp.Hu = uint32_t(c->H);
@@ -1285,8 +1309,8 @@ int render_now(hg_ctx* c, int32_t n_frames, int32_t accumulate) {
     kp.box_range = p.boxDebugDisplayRange;
     kp.default_mip = p.defaultHDRIMipLevel;
     kp.use_cube = (p.useEnvironmentCubemap > 0 && c->cube_mips > 0) ? 1 : 0;
-    kp.n_spheres = ns;
-    kp.n_meshes = nm;
+    kp.n_spheres = int32_t(p.bufferCounts.x);
+    kp.n_meshes = int32_t(p.bufferCounts.y);
     kp.first_frame = accumulate ? p.frameCount : 1;
     kp.n_frames = n_frames;
     kp.accumulate = accumulate ? 1 : 0;
@@ -1295,305 +1319,206 @@ int render_now(hg_ctx* c, int32_t n_frames, int32_t accumulate) {
     kp.rank = c->rank;
     kp.n_ranks = c->n_ranks;
     kp.n_local_tiles = c->n_local_tiles;
-    kp.stack_depth = c->stack_depth;
     kp.cube_size = c->cube_size;
     kp.cube_mips = c->cube_mips;
     std::memcpy(kp.cube_mip_offset, c->cube_mip_offset, sizeof kp.cube_mip_offset);
-    kp.spheres = static_cast<const float4*>(c->spheres.p);
-    kp.meshes = static_cast<const HgDevMesh*>(c->meshes.p);
-    kp.materials = static_cast<const float4*>(c->materials.p);
-    kp.nodes = static_cast<const float4*>(c->nodes.p);
-    kp.leaves = static_cast<const uint2*>(c->leaves.p);
-    kp.tris = static_cast<const float*>(c->tris.p);
-    kp.normals = static_cast<const float4*>(c->normals.p);
+    set_scene(kp, c, P.descent_t);
+    kp.stream_deep = P.stream_deep;
+    kp.spill_stride = P.spill_stride;
     kp.cube = static_cast<const float4*>(c->cube.p);
     kp.acc = static_cast<float4*>(c->acc.p);
-    kp.counters = static_cast<unsigned long long*>(c->counters_dev.p);
-    if (!c->counters_on) kp.counters = nullptr;
+    kp.counters = c->counters_on ? static_cast<unsigned long long*>(c->counters_dev.p) : nullptr;
+    return kp;
+}
 
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    if (int rc = event_pair(c, ev)) return rc;
-    HG_HIP(c, hipEventRecord(ev.first, c->stream));
-    // HG_KERNEL_AUTO: the streaming kernel for deep BLAS or many meshes, where traversals are long or uneven and its
-    // resumable traversal lets a lane move on without waiting for the wave's slowest one (C3; C2's 9 meshes: 4,080
-    // vs 3,891 Mpaths/s, tools/sweep_r02_ai.txt); the regenerating kernel for a few shallow meshes, where shading
-    // dominates (C5's 2 meshes: 10,407 vs 9,718).  (Round 1, before the item scheduling and the mesh records in LDS,
-    // the streaming kernel lost C2 too, tools/sweeps/sweep35.txt.)
-    const bool deep_blas = c->stack_depth > HG_DESCENT_DEEP + 2;
-    const bool stream_auto = deep_blas || c->n_meshes >= HG_STREAM_MIN_MESHES;
-    const int32_t kern = c->kernel == HG_KERNEL_AUTO ? (stream_auto ? HG_KERNEL_MEGA_STREAM : HG_KERNEL_MEGA_REGEN)
-                                                     : c->kernel;
-    // relaxed descent threshold: 3 for the regen / lockstep kernels, HG_STREAM_DESCENT_T for the streaming one
-    kp.stream_deep = deep_blas ? 1u : 0u;
-    kp.descent_t = c->descent_t >= 0 ? uint32_t(c->descent_t)
-                   : !deep_blas      ? 0u
-                   : kern == HG_KERNEL_MEGA_STREAM ? uint32_t(HG_STREAM_DESCENT_T)
-                                                   : uint32_t(HG_DESCENT_T);
-    {
-        const bool regen = (kern == HG_KERNEL_MEGA_REGEN || kern == HG_KERNEL_MEGA_STREAM) && p.halogenDebugMode == 0 &&
-                           kp.max_bounces <= HG_REGEN_MAX_BOUNCES && kp.spp < HG_REGEN_MAX_CHUNK;
-        // default block (option 128): 64 for the regenerating kernel (one tile per workgroup schedules best,
-        // tools/sweeps/sweep12.txt), 256 for the lockstep one
-        // the regenerating / streaming kernels run one wave per workgroup (their LDS row layout assumes it)
-        const int mblock = regen ? 64 : (c->block == 128 ? 256 : c->block);
-        // Frame-parallel split: `split` waves share each tile, each tracing a chunk of the frames, so a launch has
-        // about 6x (formerly 16x, 12x) as many waves as the GPU holds at once (short waves: small drain tail; a rank's 1/N share
-        // of the tiles at N GPUs still fills the GPU); the per-frame colours are then blended in frame order
-        // (bit-identical).  Measured (tools/sweeps/sweep16-17.txt): C3 1080p 1180 -> 1251 Mpaths/s at N=1, and one
-        // rank's share at N=8 314 -> 1212.
-        const bool stream_k = regen && kern == HG_KERNEL_MEGA_STREAM;
-        const int64_t tiles = c->n_local_tiles;
-        const int64_t units = tiles;  // work units: one tile per wave
-        const int64_t resident = int64_t(c->n_cu) * 4 * (stream_k ? HG_STREAM_WAVES : HG_MEGA_WAVES);
-        int split = 1;
-        if (regen && n_frames > 1 && tiles > 0) {
-            if (c->frame_split > 0) split = std::min(n_frames, int(c->frame_split));
-            // about 6 launches' worth of wave slots: with the cost order and a tile's chunks on consecutive waves
-            // (wave_unit), fewer, longer waves win: a rank's share at N=2 split 2 vs 4 -> 2,409 vs 2,308, N=8 8 vs 16
-            // -> 2,440 vs 2,337, C2 / C5 2 vs 3 -> +1.5 / +2.7 %, C3 at N=1 stays unsplit (tools/sweeps/sweep82-83.txt;
-            // the multiplier was 16, then 12 with the chunk-major cost order)
-            else split = int(std::min<int64_t>(n_frames, (6 * resident + units - 1) / units));
-            // a share that runs the queue form (HG_OPT_QUEUE_FILL, below): smaller units, about 24 per wave slot, so
-            // the launch's end leaves little behind (emulated N = 8 share of C3: split 8 / 16 / 32 -> 2,708 / 2,861 /
-            // 2,933 Mpaths/s; per-tile waves at split 8: 2,790)
-            if (c->frame_split <= 0 && kern == HG_KERNEL_MEGA_STREAM && n_frames > HG_QUEUE_MAX_FRAMES &&
-                c->queue_fill > 0 && units * n_frames < int64_t(c->queue_fill) * resident * 64)
-                split = int(std::min<int64_t>(n_frames, (int64_t(HG_QUEUE_FILL_UNITS) * resident + units - 1) / units));
-        }
-        // the AQL dispatch packet's grid size is a 32-bit count of work-items: at most 2^26 - 1 waves of 64 lanes
-        constexpr int64_t kMaxWaves = (int64_t(1) << 26) - 1;
-        if (units > kMaxWaves) {
-            c->free_events.push_back(ev);
-            return fail(c, HG_E_UNSUPPORTED, "target too large: %lld work units", (long long)units);
-        }
-        if (units > 0) split = int(std::min<int64_t>(split, kMaxWaves / units));
-        int chunk_max = HG_REGEN_MAX_CHUNK;
-        // The streaming kernel (always) and the regenerating kernel (item scheduling or a frame split) store every
-        // frame's colour and blend them into the accumulator in frame order afterwards (hg_blend_frames): such a launch
-        // is traced on a trace stream and blended on the context stream (the trace pipeline, hg_ctx.h).
-        const bool items_k = regen && (stream_k || HG_REGEN_ITEMS);
-        const bool pipelined = regen && (items_k || split > 1);
-        const size_t per_frame = size_t(tiles) * 64 * sizeof(float4);
-        if (pipelined)
-            chunk_max = int(std::max<size_t>(1, std::min<size_t>(size_t(chunk_max), kFrameColorCap / per_frame)));
-        const int mgrid = int((units * split + mblock / 64 - 1) / (mblock / 64));
-        kp.spill_stride = uint32_t(mgrid) * uint32_t(mblock);
-        // stack entries beyond the LDS part: one column per thread (the streaming kernel's LDS part may be shorter)
-        const uint32_t lds_part = std::min<uint32_t>(HG_MEGA_LDS_STACK, HG_STREAM_LDS_STACK);
-        const size_t spill_bytes =
-            kp.stack_depth > lds_part ? size_t(kp.spill_stride) * (kp.stack_depth - lds_part) * 4 : 0;
-        if (spill_bytes && !pipelined) {
-            if (int rc = ensure_quiet(c, c->spill, spill_bytes)) {
-                c->free_events.push_back(ev);
-                return rc;
-            }
-            kp.spill = static_cast<uint32_t*>(c->spill.p);
-        }
+int launch_failed(hg_ctx* c, hipError_t e) {
+    return fail(c, HG_E_HIP, "megakernel launch failed: %s", hipGetErrorString(e));
+}
 
-        c->counters.last_kernel = uint64_t(regen ? kern : HG_KERNEL_MEGA);
-        // the reference's one frame per call: posted to the render server (persistent trace waves)
-        const bool chain = accumulate && server_chain(c, n_frames);
-        if (c->server_on && stream_k && pipelined && accumulate && n_frames <= HG_QUEUE_MAX_FRAMES && tiles > 0 &&
-            (c->server_on == 2 || host_ahead(c) || chain)) {
-            const int rc = server_render(c, kp, n_frames);
-            if (rc == HG_OK) {
-                HG_HIP(c, hipEventRecord(ev.second, c->stream));
-                note_call(c);
-                c->pending.push_back(ev);
-                c->counters.launches++;
-                if (c->pending.size() + c->pending_trace.size() > 4096)
-                    if (int r = drain_events(c)) return r;
-                c->params.frameCount += n_frames;  // FrameCount++ per accumulated frame (RP:347)
-                return HG_OK;
-            }
-            if (rc != HG_E_UNSUPPORTED) {
-                c->free_events.push_back(ev);
-                return rc;
-            }
-        } else if (c->sv.running) {  // another kind of launch needs the GPU's wave slots
-            if (int rc = server_stop(c)) {
-                c->free_events.push_back(ev);
-                return rc;
-            }
+// Trace pipeline, step 1: the trace streams' buffers for a call planned as P, grown only while idle.  The streams
+// beyond HG_TRACE_LANES_BIG trace short chunks only: they get buffers when the call has such a chunk (P.short_chunks)
+int ensure_lanes(hg_ctx* c, const HgCallPlan& P) {
+    for (int li = 0; li < HG_TRACE_LANES; ++li) {
+        hg_ctx::TraceLane& L = c->lanes[li];
+        if (li >= HG_TRACE_LANES_BIG && !P.short_chunks) continue;
+        const int fmax = li < HG_TRACE_LANES_BIG ? P.big_frames : P.short_frames;
+        int rc = ensure_quiet(c, L.frame_color, P.per_frame * size_t(fmax));
+        if (!rc && P.spill_bytes) rc = ensure_quiet(c, L.spill, P.spill_bytes);
+        if (!rc && P.ordered) rc = cost_order_ensure(c, L, uint32_t(c->n_local_tiles), ensure_quiet);
+        // the queue heads are zeroed once, when allocated (each use leaves them zeroed)
+        if (!rc && P.stream_k && L.queue.bytes < HG_QUEUE_BYTES) {
+            rc = ensure_quiet(c, L.queue, HG_QUEUE_BYTES);
+            if (!rc && hipMemsetAsync(L.queue.p, 0, L.queue.bytes, L.stream) != hipSuccess)
+                rc = fail(c, HG_E_HIP, "hipMemsetAsync(queue) failed");
         }
-        hipError_t e = hipSuccess;
-        const bool ordered = pipelined && c->tile_order_on && tiles > 0;
-        const size_t tb = size_t(tiles) * sizeof(uint32_t);
-        if (pipelined) {
-            // the trace streams' buffers, grown only while idle (the lanes beyond HG_TRACE_LANES_BIG trace short chunks only)
-            // the streams beyond HG_TRACE_LANES_BIG only when this launch has a chunk of at most HG_QUEUE_MAX_FRAMES
-            // frames (the first, the last, or all of them), the rotation below that takes them
-            const int last_chunk = n_frames % chunk_max;
-            const bool short_chunks = std::min(n_frames, chunk_max) <= HG_QUEUE_MAX_FRAMES ||
-                                      (last_chunk != 0 && last_chunk <= HG_QUEUE_MAX_FRAMES);
-            for (int li = 0; li < HG_TRACE_LANES; ++li) {
-                hg_ctx::TraceLane& L = c->lanes[li];
-                if (li >= HG_TRACE_LANES_BIG && !short_chunks) continue;
-                const int fmax = std::min(n_frames, li < HG_TRACE_LANES_BIG ? chunk_max
-                                                                             : std::min(chunk_max, HG_QUEUE_MAX_FRAMES));
-                int rc = ensure_quiet(c, L.frame_color, per_frame * size_t(fmax));
-                if (!rc && spill_bytes) rc = ensure_quiet(c, L.spill, spill_bytes);
-                if (!rc && ordered) rc = ensure_quiet(c, L.tile_cost, 2 * tb);
-                if (!rc && ordered) rc = ensure_quiet(c, L.tile_order, tb);
-                // the sort's scratch and the queue heads are zeroed once, when allocated (each use leaves them zeroed)
-                const size_t osb = hg_order_scratch_bytes(uint32_t(tiles));
-                if (!rc && ordered && L.order_scratch.bytes < osb) {
-                    rc = ensure_quiet(c, L.order_scratch, osb);
-                    if (!rc && hipMemsetAsync(L.order_scratch.p, 0, L.order_scratch.bytes, L.stream) != hipSuccess)
-                        rc = fail(c, HG_E_HIP, "hipMemsetAsync(order scratch) failed");
-                }
-                const size_t qbytes = HG_QUEUE_BYTES;
-                if (!rc && stream_k && L.queue.bytes < qbytes) {
-                    rc = ensure_quiet(c, L.queue, qbytes);
-                    if (!rc && hipMemsetAsync(L.queue.p, 0, L.queue.bytes, L.stream) != hipSuccess)
-                        rc = fail(c, HG_E_HIP, "hipMemsetAsync(queue) failed");
-                }
-                if (rc) {
-                    c->free_events.push_back(ev);
-                    return rc;
-                }
-            }
-            HgKernelParams kc = kp;
-            const uint32_t slots = uint32_t(c->n_cu) * 4u * HG_STREAM_WAVES;
-            for (int done = 0; done < n_frames && e == hipSuccess;) {  // chunks at frame boundaries change nothing
-                kc.n_frames = std::min(n_frames - done, chunk_max);
-                // short chunks (the reference's one dispatch per frame) in turn on every trace stream, so that more
-                // launches' tails overlap; long ones on the first HG_TRACE_LANES_BIG (a third 64-frame launch beside
-                // two others cost C3 1.5 %)
-                int li;
-                if (kc.n_frames <= HG_QUEUE_MAX_FRAMES) {
-                    li = -1;
-                    if (c->lane_pick) {  // the first stream whose last trace and blend are done (its queue stays warm)
-                        for (int j = 0; j < HG_TRACE_LANES && li < 0; ++j)
-                            if (!c->lanes[j].blend_pending || hipEventQuery(c->lanes[j].blended) == hipSuccess) li = j;
-                        (void)hipGetLastError();  // hipErrorNotReady is a status here
-                    }
-                    if (li < 0) {
-                        li = c->next_lane;
-                        c->next_lane = (c->next_lane + 1) % HG_TRACE_LANES;
-                    }
-                } else {
-                    li = c->next_lane_big;
-                    c->next_lane_big = (c->next_lane_big + 1) % HG_TRACE_LANES_BIG;
-                }
-                hg_ctx::TraceLane& L = c->lanes[li];
-                kc.first_frame = accumulate ? kp.first_frame + done : 1;
-                kc.frame_split = std::min(split, kc.n_frames);
-                kc.frame_color = static_cast<float4*>(L.frame_color.p);
-                kc.spill = spill_bytes ? static_cast<uint32_t*>(L.spill.p) : nullptr;
-                // the persistent work-queue form for launches of few frames (the reference's one dispatch per frame),
-                // and for a launch too small to fill the GPU with 64-frame tile waves (a rank's 1/N of the image at N
-                // GPUs, HG_OPT_QUEUE_FILL): persistent waves pull (tile, frame chunk) units, so a wave's lanes drain
-                // once per launch, not once per short wave.  A share's launch of many frames fills the GPU with split
-                // tile waves instead (emulated N = 8 share of C3, 512 frames: queue 3,289, split tile waves 3,543)
-                const bool fill = c->queue_fill > 0 &&
-                                  tiles * int64_t(kc.n_frames) < int64_t(c->queue_fill) * int64_t(slots) * 64;
-                kc.queue = stream_k && (kc.n_frames <= HG_QUEUE_MAX_FRAMES || fill) ? static_cast<uint32_t*>(L.queue.p)
-                                                                                     : nullptr;
-                // Persistent waves of a queue launch.  A launch's end costs each of its waves the time its last paths
-                // take, with its lanes draining; fewer, longer-lived waves pay that less often.  So while two or more
-                // other traces are in flight (which fill the slots), a launch takes slots / min(HG_QUEUE_WAVES_DIV,
-                // traces in flight + 1); alone or beside one other (e.g. a caller that reads every frame back), all.
-                kc.resident_waves = slots;
-                if (kc.queue && HG_QUEUE_WAVES_DIV > 1) {
-                    int busy = 0;
-                    for (const hg_ctx::TraceLane& O : c->lanes)
-                        if (&O != &L && O.blend_pending && hipEventQuery(O.traced) == hipErrorNotReady) ++busy;
-                    (void)hipGetLastError();  // hipErrorNotReady is a status here, not an error for the launch check
-                    if (busy >= 2) kc.resident_waves = slots / uint32_t(std::min(HG_QUEUE_WAVES_DIV, busy + 1));
-                }
-                // Streaming launches without the queue and without a frame split: each wave traces wave_units
-                // consecutive tiles of the cost order, its lanes draining once per wave instead of once per tile
-                // (UnitItems), while the launch keeps at least HG_WAVE_UNITS_ROUNDS waves per resident slot
-                kc.wave_units = 1;
-                // (whole tiles only: a wave's units are all 8 x 8, UnitItems)
-                if (stream_k && !kc.queue && kc.frame_split == 1 && tiles > 0 && c->W % HG_TILE == 0 &&
-                    c->H % HG_TILE == 0) {
-                    const int64_t auto_wu = std::min<int64_t>(HG_WAVE_UNITS_MAX, tiles / (int64_t(HG_WAVE_UNITS_ROUNDS) * slots));
-                    kc.wave_units = uint32_t(c->wave_units > 0 ? c->wave_units : std::max<int64_t>(1, auto_wu));
-                }
-                kc.tile_order = nullptr;
-                kc.tile_cost = ordered ? static_cast<unsigned long long*>(L.tile_cost.p) : nullptr;
-                // this stream's buffers are free once the blend of its previous chunk has read them
-                if (L.blend_pending) e = hipStreamWaitEvent(L.stream, L.blended, 0);
-                if (e == hipSuccess && done == 0) e = hipEventRecord(ev.first, L.stream);  // the launch starts here
-                if (e == hipSuccess && ordered) {
-                    // Cost order, per trace stream: the stream sorts its own costs into its own order buffer (the
-                    // traces adding those costs and reading that order run on the same stream, so none is in flight
-                    // during the sort), once HG_ORDER_MIN_FRAMES frames were traced on it since its last sort:
-                    // 64-frame launches every time, the reference's 1-frame launches every 16th frame per stream.
-                    if (L.tile_cost_valid &&
-                        (!L.tile_order_valid || L.frames_since_order >= int64_t(HG_ORDER_MIN_FRAMES))) {
-                        e = hg_launch_order_tiles(kc.tile_cost, static_cast<uint32_t*>(L.tile_order.p), uint32_t(tiles),
-                                                  L.order_scratch.p,
-                                                  static_cast<unsigned long long*>(c->counters_dev.p) + 18, L.stream);
-                        L.tile_order_valid = e == hipSuccess;
-                        L.frames_since_order = 0;
-                    } else if (!L.tile_cost_valid) {
-                        e = hipMemsetAsync(kc.tile_cost, 0, size_t(tiles) * sizeof(unsigned long long), L.stream);
-                        L.tile_order_valid = false;
-                        L.frames_since_order = 0;
-                    }
-                    if (L.tile_order_valid) kc.tile_order = static_cast<const uint32_t*>(L.tile_order.p);
-                    L.tile_cost_valid = e == hipSuccess;
-                    L.frames_since_order += kc.n_frames;
-                }
-                std::pair<hipEvent_t, hipEvent_t> tev{};
-                if (e == hipSuccess && c->timing) {
-                    if (int rc = event_pair(c, tev)) {
-                        c->free_events.push_back(ev);
-                        return rc;
-                    }
-                    e = hipEventRecord(tev.first, L.stream);
-                }
-                if (e == hipSuccess)
-                    e = stream_k ? hg_launch_mega_stream(kc, mblock, c->counters_on != 0, L.stream)
-                                 : hg_launch_mega_regen(kc, mblock, c->counters_on != 0, L.stream);
-                if (c->timing && tev.first) {  // a pair goes to drain_events only with both ends recorded
-                    if (e == hipSuccess) e = hipEventRecord(tev.second, L.stream);
-                    if (e == hipSuccess) c->pending_trace.push_back(tev);
-                    else c->free_events.push_back(tev);
-                }
-                if (e == hipSuccess) e = hipEventRecord(L.traced, L.stream);
-                if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, L.traced, 0);
-                if (e == hipSuccess)  // in frame order, on the context stream
-                    e = hg_launch_blend_frames(kc, static_cast<const uint32_t*>(c->lost.p), c->stream);
-                if (e == hipSuccess) e = hipEventRecord(L.blended, c->stream);
-                L.blend_pending = e == hipSuccess;
-                done += kc.n_frames;
-            }
-            if (e != hipSuccess)  // a sort or a queue launch that failed part way may have left its words non-zero
-                for (hg_ctx::TraceLane& L : c->lanes) {
-                    if (L.queue.p) (void)hipMemsetAsync(L.queue.p, 0, L.queue.bytes, L.stream);
-                    if (L.order_scratch.p) (void)hipMemsetAsync(L.order_scratch.p, 0, L.order_scratch.bytes, L.stream);
-                    L.tile_cost_valid = L.tile_order_valid = false;
-                }
-        } else if (regen) {  // a regenerating launch that blends in the kernel (make noitems): on the context stream
-            HgKernelParams kc = kp;
-            for (int done = 0; done < n_frames && e == hipSuccess;) {
-                kc.n_frames = std::min(n_frames - done, chunk_max);
-                kc.first_frame = accumulate ? kp.first_frame + done : 1;
-                kc.frame_split = std::min(split, kc.n_frames);
-                e = hg_launch_mega_regen(kc, mblock, c->counters_on != 0, c->stream);
-                done += kc.n_frames;
-            }
-        } else {
-            e = hg_launch_mega(kp, mblock, c->counters_on != 0, c->stream);
-        }
-        if (e != hipSuccess) {
-            c->free_events.push_back(ev);
-            return fail(c, HG_E_HIP, "megakernel launch failed: %s", hipGetErrorString(e));
-        }
+        if (rc) return rc;
     }
-    HG_HIP(c, hipEventRecord(ev.second, c->stream));
-    note_call(c);
-    c->pending.push_back(ev);
-    c->counters.launches++;
-    if (c->pending.size() + c->pending_trace.size() > 4096) {
-        if (int rc = drain_events(c)) return rc;
-    }
-    if (accumulate) c->params.frameCount += n_frames;  // FrameCount++ per accumulated frame (RP:347)
     return HG_OK;
+}
+
+// Step 2: the trace stream of a chunk.  Short chunks take every stream in turn, or the first one whose last trace and
+// blend are done (HG_OPT_LANE_PICK: its queue stays warm); long ones the first HG_TRACE_LANES_BIG in turn
+hg_ctx::TraceLane& pick_lane(hg_ctx* c, bool short_stream) {
+    int li = -1;
+    if (!short_stream) {
+        li = c->next_lane_big;
+        c->next_lane_big = (c->next_lane_big + 1) % HG_TRACE_LANES_BIG;
+        return c->lanes[li];
+    }
+    if (c->lane_pick) {
+        for (int j = 0; j < HG_TRACE_LANES && li < 0; ++j)
+            if (!c->lanes[j].blend_pending || hipEventQuery(c->lanes[j].blended) == hipSuccess) li = j;
+        (void)hipGetLastError();  // hipErrorNotReady is a status here
+    }
+    if (li < 0) {
+        li = c->next_lane;
+        c->next_lane = (c->next_lane + 1) % HG_TRACE_LANES;
+    }
+    return c->lanes[li];
+}
+
+// Traces in flight on the trace streams other than L (hg_queue_waves sizes a queue launch by it)
+int traces_in_flight(hg_ctx* c, const hg_ctx::TraceLane& L) {
+    int busy = 0;
+    for (const hg_ctx::TraceLane& O : c->lanes)
+        if (&O != &L && O.blend_pending && hipEventQuery(O.traced) == hipErrorNotReady) ++busy;
+    (void)hipGetLastError();  // hipErrorNotReady is a status here, not an error for the launch check
+    return busy;
+}
+
+// Step 3: one chunk (kc: its frames) on trace stream L in the shape K: wait for the stream's buffers, sort, trace on
+// L.stream; blend in frame order on the context stream; record the events that order the next chunk.  call_start: the
+// call's timing event, for its first chunk (the launch starts there).
+int launch_chunk(hg_ctx* c, hg_ctx::TraceLane& L, HgKernelParams& kc, const HgCallPlan& P, const HgChunkPlan& K,
+                 hipEvent_t call_start) {
+    const uint32_t tiles = uint32_t(c->n_local_tiles);
+    const uint32_t slots = uint32_t(hg_wave_slots(c->n_cu, HG_STREAM_WAVES));
+    kc.frame_split = K.frame_split;
+    kc.frame_color = static_cast<float4*>(L.frame_color.p);
+    kc.spill = P.spill_bytes ? static_cast<uint32_t*>(L.spill.p) : nullptr;
+    kc.queue = K.queue ? static_cast<uint32_t*>(L.queue.p) : nullptr;
+    kc.resident_waves = K.queue && HG_QUEUE_WAVES_DIV > 1 ? hg_queue_waves(slots, traces_in_flight(c, L)) : slots;
+    kc.wave_units = K.wave_units;
+    kc.tile_order = nullptr;
+    kc.tile_cost = P.ordered ? static_cast<unsigned long long*>(L.tile_cost.p) : nullptr;
+    hipError_t e = hipSuccess;
+    // this stream's buffers are free once the blend of its previous chunk has read them
+    if (L.blend_pending) e = hipStreamWaitEvent(L.stream, L.blended, 0);
+    if (e == hipSuccess && call_start) e = hipEventRecord(call_start, L.stream);
+    if (e == hipSuccess && P.ordered) {
+        // Cost order, per trace stream: the stream sorts its own costs into its own order buffer (the traces adding
+        // those costs and reading that order run on the same stream, so none is in flight during the sort), once
+        // HG_ORDER_MIN_FRAMES frames were traced on it since its last sort: 64-frame launches every time, the
+        // reference's 1-frame launches every 16th frame per stream.  Costs not yet valid are zeroed instead.
+        const bool sort =
+            L.tile_cost_valid && (!L.tile_order_valid || L.frames_since_order >= int64_t(HG_ORDER_MIN_FRAMES));
+        if (sort || !L.tile_cost_valid) {
+            e = cost_order_run(c, L, tiles, sort);
+            L.tile_order_valid = sort && e == hipSuccess;
+            L.frames_since_order = 0;
+        }
+        if (L.tile_order_valid) kc.tile_order = static_cast<const uint32_t*>(L.tile_order.p);
+        L.tile_cost_valid = e == hipSuccess;
+        L.frames_since_order += kc.n_frames;
+    }
+    EventGuard tev(c->free_events);  // the chunk's own timing pair (HG_OPT_TIMING)
+    if (e == hipSuccess && c->timing) {
+        if (int rc = event_pair(c, tev)) return rc;
+        e = hipEventRecord(tev.pair.first, L.stream);
+    }
+    if (e == hipSuccess)
+        e = P.stream_k ? hg_launch_mega_stream(kc, P.block, c->counters_on != 0, L.stream)
+                       : hg_launch_mega_regen(kc, P.block, c->counters_on != 0, L.stream);
+    if (tev.held()) {  // a pair goes to drain_events only with both ends recorded
+        if (e == hipSuccess) e = hipEventRecord(tev.pair.second, L.stream);
+        if (e == hipSuccess) tev.hand_to(c->pending_trace);
+    }
+    if (e == hipSuccess) e = hipEventRecord(L.traced, L.stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, L.traced, 0);
+    if (e == hipSuccess)  // in frame order, on the context stream
+        e = hg_launch_blend_frames(kc, static_cast<const uint32_t*>(c->lost.p), c->stream);
+    if (e == hipSuccess) e = hipEventRecord(L.blended, c->stream);
+    L.blend_pending = e == hipSuccess;
+    return e == hipSuccess ? HG_OK : launch_failed(c, e);
+}
+
+// A pipelined call: its chunks traced on the trace streams and blended on the context stream
+int launch_pipelined(hg_ctx* c, const HgPlanIn& in, const HgCallPlan& P, const HgKernelParams& kp, hipEvent_t start) {
+    if (int rc = ensure_lanes(c, P)) return rc;
+    HgKernelParams kc = kp;
+    int rc = HG_OK;
+    for (int done = 0; done < in.n_frames && !rc; done += kc.n_frames) {  // chunks at frame boundaries change nothing
+        kc.n_frames = std::min(in.n_frames - done, P.chunk_max);
+        kc.first_frame = kp.accumulate ? kp.first_frame + done : 1;
+        const HgChunkPlan K = hg_plan_chunk(in, P, kc.n_frames);
+        rc = launch_chunk(c, pick_lane(c, K.short_stream), kc, P, K, done == 0 ? start : nullptr);
+    }
+    if (rc)  // a sort or a queue launch that failed part way may have left its words non-zero
+        for (hg_ctx::TraceLane& L : c->lanes) {
+            if (L.queue.p) (void)hipMemsetAsync(L.queue.p, 0, L.queue.bytes, L.stream);
+            if (L.order_scratch.p) (void)hipMemsetAsync(L.order_scratch.p, 0, L.order_scratch.bytes, L.stream);
+            L.tile_cost_valid = L.tile_order_valid = false;
+        }
+    return rc;
+}
+
+// After a call's work is queued on the context stream: the end of its timing pair (now drain_events'), its completion
+// event, the counts, and FrameCount++ per accumulated frame (RP:347)
+int finish_call(hg_ctx* c, EventGuard& ev, int32_t n_frames, int32_t accumulate) {
+    HG_HIP(c, hipEventRecord(ev.pair.second, c->stream));
+    note_call(c);
+    ev.hand_to(c->pending);
+    c->counters.launches++;
+    if (c->pending.size() + c->pending_trace.size() > 4096)
+        if (int rc = drain_events(c)) return rc;
+    if (accumulate) c->params.frameCount += n_frames;
+    return HG_OK;
+}
+
+// One launch of n_frames frames from FrameCount = params.frameCount (which it advances when accumulating): check,
+// plan (hg_plan.h), parameter block, then the render server or a launch of the planned shape, then the book-keeping
+int render_now(hg_ctx* c, int32_t n_frames, int32_t accumulate) {
+    if (int rc = render_check(c, n_frames)) return rc;
+    if (n_frames == 0) return HG_OK;
+    if (int rc = set_device(c)) return rc;
+    const HgPlanIn in = plan_input(c, n_frames);
+    const HgCallPlan P = hg_plan_call(in);
+    HgKernelParams kp = kernel_params(c, P, n_frames, accumulate);
+    EventGuard ev(c->free_events);  // the call's timing pair
+    if (int rc = event_pair(c, ev)) return rc;
+    HG_HIP(c, hipEventRecord(ev.pair.first, c->stream));
+    if (P.status) return fail(c, P.status, "target too large: %lld work units", (long long)c->n_local_tiles);
+    if (P.spill_bytes && !P.pipelined) {
+        if (int rc = ensure_quiet(c, c->spill, P.spill_bytes)) return rc;
+        kp.spill = static_cast<uint32_t*>(c->spill.p);
+    }
+    c->counters.last_kernel = P.last_kernel;
+    // the reference's one frame per call: posted to the render server (persistent trace waves)
+    const bool chain = accumulate && server_chain(c, n_frames);
+    if (c->server_on && P.stream_k && P.pipelined && accumulate && n_frames <= HG_QUEUE_MAX_FRAMES &&
+        c->n_local_tiles > 0 && (c->server_on == 2 || host_ahead(c) || chain)) {
+        const int rc = server_render(c, kp, n_frames);
+        if (rc == HG_OK) return finish_call(c, ev, n_frames, accumulate);
+        if (rc != HG_E_UNSUPPORTED) return rc;
+    } else if (c->sv.running) {  // another kind of launch needs the GPU's wave slots
+        if (int rc = server_stop(c)) return rc;
+    }
+    if (P.pipelined) {
+        if (int rc = launch_pipelined(c, in, P, kp, ev.pair.first)) return rc;
+    } else if (P.regen) {  // a regenerating launch that blends in the kernel (make noitems): on the context stream
+        HgKernelParams kc = kp;
+        for (int done = 0; done < n_frames; done += kc.n_frames) {
+            kc.n_frames = std::min(n_frames - done, P.chunk_max);
+            kc.first_frame = accumulate ? kp.first_frame + done : 1;
+            kc.frame_split = std::min(P.split, kc.n_frames);
+            const hipError_t e = hg_launch_mega_regen(kc, P.block, c->counters_on != 0, c->stream);
+            if (e != hipSuccess) return launch_failed(c, e);
+        }
+    } else {
+        const hipError_t e = hg_launch_mega(kp, P.block, c->counters_on != 0, c->stream);
+        if (e != hipSuccess) return launch_failed(c, e);
+    }
+    return finish_call(c, ev, n_frames, accumulate);
 }
 
 }  // namespace
@@ -1821,21 +1746,6 @@ int hg_pack_display(const float* rgba, size_t n_pixels, int32_t format, void* ou
     return HG_OK;
 }
 
-namespace {
-// Frames of consecutive calls held for one launch (HG_OPT_COALESCE).  A rank's share of the image (N > 1) holds until
-// its launch fills the GPU as one context's launch of the whole image does (HG_SHARE_HOLD_ROUNDS): a 1/8 share's
-// 64-frame launch has 4,050 tiles for 5,120 wave slots, and its tail is as long as a full launch's.
-int32_t hold_window(const hg_ctx* c) {
-    int64_t w = c->coalesce;
-    if (w > 1 && c->n_ranks > 1 && c->n_local_tiles > 0) {
-        const int64_t slots = int64_t(c->n_cu) * 4 * HG_STREAM_WAVES;
-        const int64_t share = (int64_t(HG_SHARE_HOLD_ROUNDS) * slots * 64 + c->n_local_tiles - 1) / c->n_local_tiles;
-        w = std::max(w, std::min<int64_t>(share, HG_SHARE_HOLD_MAX));
-    }
-    return int32_t(w);
-}
-}  // namespace
-
 int hg_render(hg_ctx* c, int32_t n_frames, int32_t accumulate) {
     if (!c) return HG_E_INVALID;
     if (int rc = render_check(c, n_frames)) return rc;
@@ -1849,7 +1759,7 @@ int hg_render(hg_ctx* c, int32_t n_frames, int32_t accumulate) {
     // entry point flushes first)
     c->pending_acc = accumulate;
     c->pending_frames += n_frames;
-    return c->pending_frames >= hold_window(c) ? hg_ctx_flush(c) : HG_OK;
+    return c->pending_frames >= hg_hold_window(plan_input(c, c->pending_frames)) ? hg_ctx_flush(c) : HG_OK;
 }
 
 int hg_synchronize(hg_ctx* c) {
@@ -1883,20 +1793,7 @@ int hg_readback(hg_ctx* c, float* rgba, size_t n_floats) {
         HG_HIP(c, hipMemcpyAsync(tiles.data(), c->acc.p, tiles.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     HG_HIP(c, hipStreamSynchronize(c->stream));
     if (int rc = drain_events(c)) return rc;
-    for (int32_t lt = 0; lt < c->n_local_tiles; ++lt) {
-        const int64_t gt = int64_t(c->rank) + int64_t(lt) * c->n_ranks;
-        const int tx = int(gt % c->tiles_x), ty = int(gt / c->tiles_x);
-        for (int l = 0; l < 64; ++l) {
-            const int x = tx * HG_TILE + (l & 7), y = ty * HG_TILE + (l >> 3);
-            if (x >= c->W || y >= c->H) continue;
-            const float4 v = tiles[size_t(lt) * 64 + l];
-            float* d = rgba + (size_t(y) * c->W + x) * 4;
-            d[0] = v.x;
-            d[1] = v.y;
-            d[2] = v.z;
-            d[3] = v.w;
-        }
-    }
+    for_local_pixels(c, [&](size_t slot, size_t pixel) { std::memcpy(rgba + pixel * 4, &tiles[slot], sizeof(float4)); });
     return lost_check(c);
 }
 
@@ -1909,16 +1806,7 @@ int hg_set_accumulation(hg_ctx* c, const float* rgba, size_t n_floats, int32_t f
     if (int rc = set_device(c)) return rc;
     // the tile-major repack of hg_readback, inverted; slots of an edge tile outside the image hold 0, as after a clear
     std::vector<float4> tiles(size_t(c->n_local_tiles) * 64, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    for (int32_t lt = 0; lt < c->n_local_tiles; ++lt) {
-        const int64_t gt = int64_t(c->rank) + int64_t(lt) * c->n_ranks;
-        const int tx = int(gt % c->tiles_x), ty = int(gt / c->tiles_x);
-        for (int l = 0; l < 64; ++l) {
-            const int x = tx * HG_TILE + (l & 7), y = ty * HG_TILE + (l >> 3);
-            if (x >= c->W || y >= c->H) continue;
-            const float* s = rgba + (size_t(y) * c->W + x) * 4;
-            tiles[size_t(lt) * 64 + l] = make_float4(s[0], s[1], s[2], s[3]);
-        }
-    }
+    for_local_pixels(c, [&](size_t slot, size_t pixel) { std::memcpy(&tiles[slot], rgba + pixel * 4, sizeof(float4)); });
     if (!tiles.empty())
         HG_HIP(c, hipMemcpyAsync(c->acc.p, tiles.data(), tiles.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     if (int rc = reset_lost(c)) return rc;
@@ -2125,16 +2013,7 @@ int query_params(hg_ctx* c, uint32_t threads, HgKernelParams& kp) {
     kp.far_ = HG_INF;
     kp.n_spheres = c->n_spheres;
     kp.n_meshes = c->n_meshes;
-    kp.stack_depth = c->stack_depth;
-    const bool deep_blas = c->stack_depth > HG_DESCENT_DEEP + 2;
-    kp.descent_t = c->descent_t >= 0 ? uint32_t(c->descent_t) : deep_blas ? uint32_t(HG_DESCENT_T) : 0u;
-    kp.spheres = static_cast<const float4*>(c->spheres.p);
-    kp.meshes = static_cast<const HgDevMesh*>(c->meshes.p);
-    kp.materials = static_cast<const float4*>(c->materials.p);
-    kp.nodes = static_cast<const float4*>(c->nodes.p);
-    kp.leaves = static_cast<const uint2*>(c->leaves.p);
-    kp.tris = static_cast<const float*>(c->tris.p);
-    kp.normals = static_cast<const float4*>(c->normals.p);
+    set_scene(kp, c, hg_descent_t(c->descent_t, c->stack_depth, HG_KERNEL_MEGA));
     kp.spill_stride = threads;
     const uint32_t lds_part = hg_query_lds_stack();
     if (kp.stack_depth > lds_part) {  // one spill column per thread (the context is idle: the buffer may move)

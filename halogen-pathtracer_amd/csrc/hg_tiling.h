@@ -33,6 +33,30 @@ HG_HD HgPixelSource hg_pixel_source(uint32_t x, uint32_t y, uint32_t tiles_x, ui
     return HgPixelSource{g % n_ranks, g / n_ranks, (x & 7u) + 8u * (y & 7u)};
 }
 
+struct HgTileOrigin {
+    uint32_t x, y;  // image pixel of the tile's lane 0 (an edge tile may reach beyond the image)
+};
+
+// The inverse: where local tile `local_tile` of `rank` lies in the image (global tile rank + local_tile * n_ranks)
+HG_HD HgTileOrigin hg_tile_origin(uint32_t local_tile, uint32_t rank, uint32_t n_ranks, uint32_t tiles_x) {
+    const uint64_t g = uint64_t(rank) + uint64_t(local_tile) * n_ranks;
+    return HgTileOrigin{uint32_t(g % tiles_x) * 8u, uint32_t(g / tiles_x) * 8u};
+}
+
+// Visit the pixels inside the W x H image of a rank's n_local_tiles local tiles: f(accumulator slot, image pixel),
+// slot = local_tile * 64 + lane, pixel = y * W + x.  Slots of an edge tile beyond the image are not visited.
+template <class F>
+inline void hg_for_local_pixels(uint32_t W, uint32_t H, uint32_t n_local_tiles, uint32_t rank, uint32_t n_ranks, F&& f) {
+    const uint32_t tiles_x = (W + 7u) / 8u;
+    for (uint32_t lt = 0; lt < n_local_tiles; ++lt) {
+        const HgTileOrigin o = hg_tile_origin(lt, rank, n_ranks, tiles_x);
+        for (uint32_t l = 0; l < 64u; ++l) {
+            const uint32_t x = o.x + (l & 7u), y = o.y + (l >> 3);
+            if (x < W && y < H) f(size_t(lt) * 64u + l, size_t(y) * W + x);
+        }
+    }
+}
+
 // float4 index of a pixel source in the [rank][slab_tiles][64] staging layout
 HG_HD size_t hg_slab_index(const HgPixelSource& s, uint32_t slab_tiles) {
     return (size_t(s.rank) * slab_tiles + s.local_tile) * 64u + s.lane;

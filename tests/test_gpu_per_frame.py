@@ -160,6 +160,45 @@ def test_gpu_checkpoint_resume_bit_identical(gpu, name):
 
 
 @pytest.mark.gpu
+def test_gpu_tiled_readback_and_checkpoint_ragged(gpu):
+    """33 x 17 (5 x 3 tiles, ragged on both edges) cut 3 ways: each rank's hg_readback writes exactly its own pixels
+    (the rest of the caller's buffer keeps its bits), the ranks' pixels together are the 1-rank image bit for bit, and
+    hg_set_accumulation -> hg_readback of arbitrary bits on rank 1 of 3 returns the owned pixels unchanged."""
+    W, H, N = 33, 17, 3
+    cfg = scenes.CONFIGS["C1"].resized(W, H, 2)
+    s = rp.clamp_settings(scenes.settings_for(cfg))
+    packed = cases._scene(cfg.scene, 10)
+    params = rp.make_params(s, cfg.camera(), 1, len(packed.spheres), len(packed.meshes), False)
+    full, _ = gpu_render(packed, params, 2, True)
+    assert not np.isnan(full).any()
+    yy, xx = np.mgrid[0:H, 0:W]
+    owner = ((yy // 8) * ((W + 7) // 8) + xx // 8) % N  # csrc/hg_tiling.h: global tile g belongs to rank g % N
+    fill = np.uint32(0x7FC0BEEF)  # a NaN with a payload no render produces
+    whole = np.zeros((H, W, 4), np.float32)
+    for r in range(N):
+        with abi.Context(0) as ctx:
+            ctx.upload_scene(packed)
+            ctx.resize(W, H)
+            ctx.set_tiling(r, N)
+            ctx.set_params(params)
+            ctx.render(2, True)
+            img = np.full((H, W, 4), fill, np.uint32).view(np.float32)
+            ctx.readback(W, H, img)
+            assert (owner == r).any()
+            assert_bitwise(img[owner == r], full[owner == r], f"rank {r} of {N}: its own pixels")
+            assert (img.view(np.uint32)[owner != r] == fill).all(), f"rank {r} wrote pixels it does not own"
+            whole[owner == r] = img[owner == r]  # (the sum over the ranks; copied, since -0 + 0 would lose a sign)
+            if r == 1:
+                bits = np.random.default_rng(33).integers(0, 1 << 32, (H, W, 4), dtype=np.uint64).astype(np.uint32)
+                ctx.set_accumulation(bits.view(np.float32), 5)
+                back = np.full((H, W, 4), fill, np.uint32).view(np.float32)
+                ctx.readback(W, H, back)
+                assert (back.view(np.uint32)[owner == r] == bits[owner == r]).all(), "checkpoint round trip"
+                assert (back.view(np.uint32)[owner != r] == fill).all()
+    assert_bitwise(whole, full, "the ranks' pixels together")
+
+
+@pytest.mark.gpu
 def test_gpu_render_pass_restore(gpu):
     """HalogenRenderPass.restore(read_image(), getFrameCount()) on a new pass continues bit-identically."""
     cfg = scenes.CONFIGS["C1"].resized(40, 32, 3)

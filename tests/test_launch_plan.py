@@ -1,0 +1,440 @@
+"""The launch plan of hg_render (csrc/hg_plan.h): which kernel runs, the frame split, the chunk length, queue form or
+per-tile waves, the trace stream class, spill bytes, the hold window and the render server's sizing.  Every plan renders
+the same image, so a wrong plan only runs slower and no rendering test can see it: here the header is compiled with g++
+(no HIP, no GPU) and checked against the values the code comments state for a 256-CU GPU, against a Python restatement
+of the arithmetic as hg_runtime.hip had it before the plan was split out, and the server's unit -> frame magic divide
+against integer division.  Also the inverse tile mapping of csrc/hg_tiling.h and the event-pair scope guard of
+csrc/hg_pair_guard.h, through the same driver."""
+import random
+import subprocess
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parents[1]
+CSRC = ROOT / "halogen-pathtracer_amd" / "csrc"
+INCLUDE = ROOT / "include"
+
+DRIVER = r'''
+#include "hg_plan.h"
+#include "hg_tiling.h"
+#include "hg_pair_guard.h"
+#include <cstdio>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+static void chunk(const HgPlanIn& in, const HgCallPlan& P, int frames) {
+    const HgChunkPlan k = hg_plan_chunk(in, P, frames);
+    std::printf(" %d %d %d %u %d", frames, k.frame_split, int(k.queue), k.wave_units, int(k.short_stream));
+}
+
+static void plan() {
+    HgPlanIn in{};
+    int busy, sv_waves;
+    if (std::scanf("%d %d %d %d %u %d %d %d %d %d %d %d %d %d %d %u %u %u %d %d %d", &in.n_cu, &in.n_local_tiles, &in.W,
+                   &in.H, &in.stack_depth, &in.n_meshes, &in.kernel, &in.block, &in.frame_split, &in.wave_units,
+                   &in.queue_fill, &in.descent_t, &in.tile_order_on, &in.coalesce, &in.n_ranks, &in.debug_mode,
+                   &in.max_bounces, &in.spp, &in.n_frames, &busy, &sv_waves) != 21)
+        return;
+    const HgCallPlan P = hg_plan_call(in);
+    std::printf("%d", P.status);
+    if (P.status == HG_OK) {
+        std::printf(" %d %llu %d %d %d %d %d %u %u %d %d %d %d %u %zu %zu %d %d %d", P.kernel,
+                    (unsigned long long)P.last_kernel, int(P.regen), int(P.stream_k), int(P.items_k), int(P.pipelined),
+                    int(P.ordered), P.stream_deep, P.descent_t, P.block, P.split, P.chunk_max, P.grid, P.spill_stride,
+                    P.per_frame, P.spill_bytes, int(P.short_chunks), P.big_frames, P.short_frames);
+        const int last = in.n_frames % P.chunk_max;
+        chunk(in, P, std::min(in.n_frames, P.chunk_max));  // the first chunk
+        chunk(in, P, last ? last : std::min(in.n_frames, P.chunk_max));  // the last
+    }
+    const uint32_t slots = uint32_t(hg_wave_slots(in.n_cu, HG_STREAM_WAVES));
+    const HgServerPlan S = hg_plan_server(in.n_cu, uint32_t(in.n_local_tiles), in.stack_depth, sv_waves);
+    std::printf(" %d %u %u %u %u %zu %zu %u %u %u\n", hg_hold_window(in), hg_queue_waves(slots, busy), S.ring, S.slots,
+                S.grid, S.per_frame, S.spill_bytes, S.frames_cap, S.div_magic, S.div_shift);
+}
+
+// unit -> frame as hg_mega.hip sv_frame computes it
+static void divide() {
+    unsigned tiles, n;
+    if (std::scanf("%u %u", &tiles, &n) != 2) return;
+    const HgServerPlan S = hg_plan_server(256, tiles, 2, 5);
+    unsigned long long bad = 0;
+    for (unsigned i = 0; i < n; ++i) {
+        unsigned u;
+        if (std::scanf("%u", &u) != 1) return;
+        const uint32_t q = S.div_magic ? uint32_t((uint64_t(u) * S.div_magic) >> 32) >> S.div_shift : u >> S.div_shift;
+        if (q != u / tiles && !bad++) std::printf("tiles %u u %u: %u != %u ", tiles, u, q, u / tiles);
+    }
+    std::printf("%llu %d\n", bad, int(S.div_magic == 0u));
+}
+
+// every pixel of a W x H image is visited exactly once, by its owner, at the slot hg_pixel_source names
+static void tiling() {
+    unsigned n, W, H;
+    if (std::scanf("%u %u %u", &n, &W, &H) != 3) return;
+    const uint32_t tiles_x = (W + 7) / 8, tiles_y = (H + 7) / 8;
+    std::vector<std::vector<int64_t>> at(n);  // per rank and slot: the pixel it was visited for (-1: never)
+    uint64_t visits = 0, twice = 0, wrong = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+        const uint32_t n_local = uint32_t(hg_rank_tiles(int64_t(tiles_x) * tiles_y, int32_t(r), int32_t(n)));
+        at[r].assign(size_t(n_local) * 64, -1);
+        hg_for_local_pixels(W, H, n_local, r, n, [&](size_t slot, size_t pixel) {
+            ++visits;
+            if (at[r][slot] >= 0) ++twice;
+            at[r][slot] = int64_t(pixel);
+        });
+    }
+    for (uint32_t y = 0; y < H; ++y)
+        for (uint32_t x = 0; x < W; ++x) {
+            const HgPixelSource s = hg_pixel_source(x, y, tiles_x, n);
+            const HgTileOrigin o = hg_tile_origin(s.local_tile, s.rank, n, tiles_x);
+            const size_t slot = size_t(s.local_tile) * 64 + s.lane;
+            if (s.rank >= n || slot >= at[s.rank].size() || at[s.rank][slot] != int64_t(y) * W + x ||
+                o.x != (x & ~7u) || o.y != (y & ~7u))
+                ++wrong;
+        }
+    // visits == W * H with every pixel found: no slot outside the image was visited
+    std::printf("%llu %llu %llu\n", (unsigned long long)visits, (unsigned long long)twice, (unsigned long long)wrong);
+}
+
+// the scope guard with a stub pair: where a pair held by a guard ends up on each exit path
+using Pair = std::pair<int, int>;
+struct Lists {
+    std::vector<Pair> free_list, pending;
+};
+static int early_return(Lists& l, bool fail_first, bool fail_second) {
+    HgPairGuard<Pair> g(l.free_list);
+    if (fail_first) return -1;  // before a pair is taken: nothing to give back
+    g.hold(Pair{7, 8});
+    if (fail_second) return -2;  // (an HG_HIP return after the pair is taken)
+    g.hand_to(l.pending);
+    g.hand_to(l.pending);  // a second hand-over does nothing
+    return 0;
+}
+static void guard() {
+    for (int k = 0; k < 5; ++k) {
+        Lists l;
+        int rc = 0;
+        if (k < 3) rc = early_return(l, k == 0, k == 1);
+        if (k == 3) {  // dismissed by hand: back to the free list once, not again by the destructor
+            HgPairGuard<Pair> g(l.free_list);
+            g.hold(Pair{7, 8});
+            g.hand_to(l.free_list);
+        }
+        if (k == 4) {  // a second pair taken by one guard: the first goes back
+            HgPairGuard<Pair> g(l.free_list);
+            g.hold(Pair{7, 8});
+            g.hold(Pair{9, 10});
+            g.hand_to(l.pending);
+        }
+        std::printf("%d free", rc);
+        for (const Pair& p : l.free_list) std::printf(" %d,%d", p.first, p.second);
+        std::printf(" pending");
+        for (const Pair& p : l.pending) std::printf(" %d,%d", p.first, p.second);
+        std::printf("\n");
+    }
+}
+
+int main() {
+    char what[16];
+    while (std::scanf("%15s", what) == 1) {
+        if (!std::strcmp(what, "plan")) plan();
+        else if (!std::strcmp(what, "divide")) divide();
+        else if (!std::strcmp(what, "tiling")) tiling();
+        else if (!std::strcmp(what, "guard")) guard();
+        else return 2;
+    }
+}
+'''
+
+# the defaults of csrc/hg_tunables.h (the Makefile passes the same HG_MEGA_WAVES / HG_MEGA_LDS_STACK)
+STREAM_WAVES, MEGA_WAVES, DESCENT_DEEP, DESCENT_T, STREAM_DESCENT_T, STREAM_MIN_MESHES = 5, 6, 16, 3, 12, 4
+REGEN_MAX_BOUNCES, REGEN_MAX_CHUNK, QUEUE_MAX_FRAMES, QUEUE_FILL_UNITS, QUEUE_WAVES_DIV = 250, 65535, 8, 24, 8
+WAVE_UNITS_MAX, WAVE_UNITS_ROUNDS, SHARE_HOLD_ROUNDS, SHARE_HOLD_MAX = 1, 3, 6, 1024
+MEGA_LDS_STACK, STREAM_LDS_STACK, SV_RING, FRAME_COLOR_CAP = 16, 12, 16, 4 << 30
+K_MEGA, K_REGEN, K_STREAM, K_AUTO = 0, 2, 3, 5
+E_UNSUPPORTED = -6
+
+FIELDS = ("n_cu tiles W H stack_depth n_meshes kernel block frame_split wave_units queue_fill descent_t tile_order_on "
+          "coalesce n_ranks debug_mode max_bounces spp n_frames busy sv_waves").split()
+CALL_OUT = ("kernel last_kernel regen stream_k items_k pipelined ordered stream_deep descent_t block split chunk_max "
+            "grid spill_stride per_frame spill_bytes short_chunks big_frames short_frames").split()
+CHUNK_OUT = "frames frame_split queue wave_units short_stream".split()
+TAIL_OUT = ("hold_window queue_waves sv_ring sv_slots sv_grid sv_per_frame sv_spill_bytes sv_frames_cap sv_div_magic "
+            "sv_div_shift").split()
+
+
+def case(**kw):
+    """Plan inputs: the defaults of a fresh context on a 256-CU GPU with C3's deep BLAS at 1080p."""
+    d = dict(n_cu=256, tiles=32400, W=1920, H=1080, stack_depth=24, n_meshes=1, kernel=K_AUTO, block=128,
+             frame_split=0, wave_units=0, queue_fill=1, descent_t=-1, tile_order_on=1, coalesce=32, n_ranks=1,
+             debug_mode=0, max_bounces=8, spp=1, n_frames=64, busy=0, sv_waves=5)
+    assert set(kw) <= set(d)
+    d.update(kw)
+    return d
+
+
+@pytest.fixture(scope="module", params=[1, 0], ids=["items", "noitems"])
+def driver(request, tmp_path_factory):
+    """The driver with the default tunables and, as `make noitems` builds the library, with -DHG_REGEN_ITEMS=0."""
+    d = tmp_path_factory.mktemp("plan")
+    (d / "main.cpp").write_text(DRIVER)
+    exe = d / "plan"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall",f"-I{CSRC}", f"-I{INCLUDE}",
+                    f"-DHG_REGEN_ITEMS={request.param}", "-DHG_MEGA_WAVES=6", "-DHG_MEGA_LDS_STACK=16",
+                    str(d / "main.cpp"), "-o", str(exe)], check=True)
+    return exe, request.param
+
+
+def run(exe, text):
+    return subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+
+
+def plans(exe, cases):
+    """The header's decisions for each case, as a dict of named integers (a refused call: status and the tail only)."""
+    lines = run(exe, "".join("plan " + " ".join(str(c[f]) for f in FIELDS) + "\n" for c in cases))
+    assert len(lines) == len(cases)
+    out = []
+    for line in lines:
+        v = [int(x) for x in line.split()]
+        d = {"status": v[0]}
+        if v[0] == 0:
+            names = CALL_OUT + ["first_" + n for n in CHUNK_OUT] + ["last_" + n for n in CHUNK_OUT] + TAIL_OUT
+        else:
+            names = TAIL_OUT
+        assert len(v) == 1 + len(names)
+        d.update(zip(names, v[1:]))
+        out.append(d)
+    return out
+
+
+def slots_of(n_cu, waves):
+    return n_cu * 4 * waves
+
+
+def restate_chunk(c, P, frames, prefix):
+    """hg_runtime.hip render_now's per-chunk decisions, as they stood in the chunk loop of its pipelined branch."""
+    tiles, slots = c["tiles"], slots_of(c["n_cu"], STREAM_WAVES)
+    frame_split = min(P["split"], frames)
+    fill = c["queue_fill"] > 0 and tiles * frames < c["queue_fill"] * slots * 64
+    queue = bool(P["stream_k"]) and (frames <= QUEUE_MAX_FRAMES or fill)
+    wave_units = 1
+    if P["stream_k"] and not queue and frame_split == 1 and tiles > 0 and c["W"] % 8 == 0 and c["H"] % 8 == 0:
+        auto_wu = min(WAVE_UNITS_MAX, tiles // (WAVE_UNITS_ROUNDS * slots))
+        wave_units = c["wave_units"] if c["wave_units"] > 0 else max(1, auto_wu)
+    return {prefix + "frames": frames, prefix + "frame_split": frame_split, prefix + "queue": int(queue),
+            prefix + "wave_units": wave_units, prefix + "short_stream": int(frames <= QUEUE_MAX_FRAMES)}
+
+
+def restate(c, items):
+    """The decisions of render_now, hold_window and server_start restated from hg_runtime.hip as it was before
+    hg_plan.h, in the order of its lines (tiles >= 1)."""
+    tiles, n_frames, n_cu = c["tiles"], c["n_frames"], c["n_cu"]
+    # hold_window
+    w = c["coalesce"]
+    if w > 1 and c["n_ranks"] > 1 and tiles > 0:
+        share = (SHARE_HOLD_ROUNDS * slots_of(n_cu, STREAM_WAVES) * 64 + tiles - 1) // tiles
+        w = max(w, min(share, SHARE_HOLD_MAX))
+    # queue waves (the chunk loop's resident_waves)
+    slots = slots_of(n_cu, STREAM_WAVES)
+    queue_waves = slots // min(QUEUE_WAVES_DIV, c["busy"] + 1) if c["busy"] >= 2 else slots
+    # server_start
+    per_frame = tiles * 64 * 16
+    ring = SV_RING
+    while ring > 2 and ring * per_frame > (2 << 30):
+        ring >>= 1
+    sv_slots = slots_of(n_cu, c["sv_waves"])
+    sv_grid = min(tiles, sv_slots)
+    sv_spill = sv_grid * 64 * (c["stack_depth"] - STREAM_LDS_STACK) * 4 if c["stack_depth"] > STREAM_LDS_STACK else 0
+    if tiles & (tiles - 1) == 0:
+        magic, shift = 0, tiles.bit_length() - 1
+    else:
+        shift = tiles.bit_length() - 1
+        magic = (((1 << (32 + shift)) + tiles - 1) // tiles) & 0xFFFFFFFF
+    tail = dict(hold_window=w, queue_waves=queue_waves, sv_ring=ring, sv_slots=sv_slots, sv_grid=sv_grid,
+                sv_per_frame=per_frame, sv_spill_bytes=sv_spill, sv_frames_cap=min(1 << 24, (1 << 31) // max(tiles, 1)),
+                sv_div_magic=magic, sv_div_shift=shift)
+    # render_now
+    deep_blas = c["stack_depth"] > DESCENT_DEEP + 2
+    stream_auto = deep_blas or c["n_meshes"] >= STREAM_MIN_MESHES
+    kern = (K_STREAM if stream_auto else K_REGEN) if c["kernel"] == K_AUTO else c["kernel"]
+    if c["descent_t"] >= 0:
+        descent_t = c["descent_t"]
+    elif not deep_blas:
+        descent_t = 0
+    else:
+        descent_t = STREAM_DESCENT_T if kern == K_STREAM else DESCENT_T
+    regen = (kern in (K_REGEN, K_STREAM) and c["debug_mode"] == 0 and c["max_bounces"] <= REGEN_MAX_BOUNCES and
+             c["spp"] < REGEN_MAX_CHUNK)
+    mblock = 64 if regen else (256 if c["block"] == 128 else c["block"])
+    stream_k = regen and kern == K_STREAM
+    units = tiles
+    resident = slots_of(n_cu, STREAM_WAVES if stream_k else MEGA_WAVES)
+    split = 1
+    if regen and n_frames > 1 and tiles > 0:
+        if c["frame_split"] > 0:
+            split = min(n_frames, c["frame_split"])
+        else:
+            split = min(n_frames, (6 * resident + units - 1) // units)
+        if (c["frame_split"] <= 0 and kern == K_STREAM and n_frames > QUEUE_MAX_FRAMES and c["queue_fill"] > 0 and
+                units * n_frames < c["queue_fill"] * resident * 64):
+            split = min(n_frames, (QUEUE_FILL_UNITS * resident + units - 1) // units)
+    max_waves = (1 << 26) - 1
+    if units > max_waves:
+        return dict(tail, status=E_UNSUPPORTED)
+    if units > 0:
+        split = min(split, max_waves // units)
+    chunk_max = REGEN_MAX_CHUNK
+    items_k = regen and (stream_k or bool(items))
+    pipelined = regen and (items_k or split > 1)
+    if pipelined:
+        chunk_max = max(1, min(chunk_max, FRAME_COLOR_CAP // per_frame))
+    mgrid = (units * split + mblock // 64 - 1) // (mblock // 64)
+    spill_stride = (mgrid * mblock) & 0xFFFFFFFF
+    lds_part = min(MEGA_LDS_STACK, STREAM_LDS_STACK)
+    spill_bytes = spill_stride * (c["stack_depth"] - lds_part) * 4 if c["stack_depth"] > lds_part else 0
+    ordered = pipelined and c["tile_order_on"] != 0 and tiles > 0
+    last_chunk = n_frames % chunk_max
+    short_chunks = min(n_frames, chunk_max) <= QUEUE_MAX_FRAMES or (last_chunk != 0 and last_chunk <= QUEUE_MAX_FRAMES)
+    P = dict(status=0, kernel=kern, last_kernel=kern if regen else K_MEGA, regen=int(regen), stream_k=int(stream_k),
+             items_k=int(items_k), pipelined=int(pipelined), ordered=int(ordered), stream_deep=int(deep_blas),
+             descent_t=descent_t, block=mblock, split=split, chunk_max=chunk_max, grid=mgrid, spill_stride=spill_stride,
+             per_frame=per_frame, spill_bytes=spill_bytes, short_chunks=int(short_chunks),
+             big_frames=min(n_frames, chunk_max), short_frames=min(n_frames, min(chunk_max, QUEUE_MAX_FRAMES)))
+    first = min(n_frames, chunk_max)
+    P.update(restate_chunk(c, P, first, "first_"))
+    P.update(restate_chunk(c, P, last_chunk if last_chunk else first, "last_"))
+    P.update(tail)
+    return P
+
+
+def test_anchors(driver):
+    """The values the comments of hg_tunables.h / hg_plan.h and profiles/ state for n_cu = 256 (5,120 wave slots of the
+    streaming kernel), each checked by hand against the arithmetic of the restatement above."""
+    exe, items = driver
+    cases = [
+        case(),                                                      # 0: C3, the whole 1080p image, 64 frames
+        case(n_frames=1),                                            # 1: the same, the reference's 1 frame per call
+        case(tiles=4050, n_ranks=8),                                 # 2: a 1/8 share
+        case(tiles=4050, n_ranks=8, queue_fill=0),                   # 3
+        case(tiles=8100, n_ranks=4), case(tiles=16200, n_ranks=2),   # 4, 5: hold windows
+        case(tiles=65536, W=2048, H=2048, stack_depth=8, kernel=K_REGEN, n_frames=65, frame_split=3),  # 6
+        case(stack_depth=10, n_meshes=2), case(stack_depth=10, n_meshes=4), case(stack_depth=19, n_meshes=1),  # 7-9
+        case(stack_depth=18, n_meshes=1),                            # 10: HG_DESCENT_DEEP + 2 is not deep
+        case(debug_mode=3), case(max_bounces=251), case(spp=65535), case(max_bounces=250, spp=65534),  # 11-14
+        case(debug_mode=1, block=64),                                # 15
+    ]
+    p = plans(exe, cases)
+    c3 = p[0]
+    assert (c3["status"], c3["kernel"], c3["last_kernel"], c3["stream_k"], c3["pipelined"]) == (0, K_STREAM, K_STREAM, 1, 1)
+    assert (c3["split"], c3["chunk_max"], c3["per_frame"]) == (1, 129, 32400 * 1024)  # 4 GiB over 32,400 KiB
+    assert (c3["first_queue"], c3["first_wave_units"], c3["first_short_stream"], c3["first_frame_split"]) == (0, 1, 0, 1)
+    assert (c3["stream_deep"], c3["descent_t"], c3["block"], c3["grid"]) == (1, 12, 64, 32400)
+    assert c3["short_chunks"] == 0 and c3["hold_window"] == 32  # N = 1 holds HG_OPT_COALESCE frames
+    one = p[1]
+    assert (one["split"], one["first_queue"], one["first_short_stream"], one["short_chunks"]) == (1, 1, 1, 1)
+    assert (one["big_frames"], one["short_frames"]) == (1, 1)
+    share = p[2]  # about 24 units per wave slot
+    assert share["split"] == (24 * 5120 + 4049) // 4050 == 31 and share["first_queue"] == 1
+    assert share["first_frame_split"] == 31 and share["grid"] == 31 * 4050
+    assert (p[3]["split"], p[3]["first_queue"], p[3]["first_wave_units"]) == (8, 0, 1)  # per-tile waves
+    # 8 / 4 / 2 calls of 64 frames (HG_SHARE_HOLD_ROUNDS)
+    assert [p[k]["hold_window"] for k in (2, 4, 5, 0)] == [486, 243, 122, 32]
+    big = p[6]  # tests/test_gpu_regen_noitems.py: chunks of 64 and 1 frames with splits 3 and 1
+    assert (big["kernel"], big["pipelined"], big["items_k"], big["chunk_max"]) == (K_REGEN, 1, items, 64)
+    assert (big["first_frames"], big["first_frame_split"], big["last_frames"], big["last_frame_split"]) == (64, 3, 1, 1)
+    assert (big["short_chunks"], big["first_queue"], big["last_queue"]) == (1, 0, 0)
+    assert [p[k]["kernel"] for k in (7, 8, 9, 10)] == [K_REGEN, K_STREAM, K_STREAM, K_REGEN]
+    assert [p[k]["stream_deep"] for k in (7, 8, 9, 10)] == [0, 0, 1, 0]
+    for k in (11, 12, 13):  # the lockstep kernel: workgroup 256 for the default block option
+        assert (p[k]["regen"], p[k]["last_kernel"], p[k]["block"], p[k]["pipelined"]) == (0, K_MEGA, 256, 0)
+        assert p[k]["grid"] == 32400 // 4 and p[k]["spill_stride"] == 32400 * 64
+    assert (p[14]["regen"], p[14]["last_kernel"]) == (1, K_STREAM)
+    assert (p[15]["block"], p[15]["grid"]) == (64, 32400)
+
+
+def test_refusal_and_grid_limit(driver):
+    """More than 2^26 - 1 work units is refused as a status; below, the split keeps the grid within the limit."""
+    exe, _ = driver
+    lim = (1 << 26) - 1
+    cases = [case(tiles=t, n_frames=f, frame_split=s) for t in (lim + 1, 1 << 27) for f in (1, 64) for s in (0, 3)]
+    assert all(p["status"] == E_UNSUPPORTED for p in plans(exe, cases))
+    cases = [case(tiles=t, n_frames=f, frame_split=s, kernel=k)
+             for t in (lim, lim // 2, lim // 2 + 1, lim // 3, 1 << 25, 1 << 20, 4050, 1)
+             for f in (1, 2, 64, 70000) for s in (0, 3, 64) for k in (K_REGEN, K_STREAM)]
+    for c, p in zip(cases, plans(exe, cases)):
+        assert p["status"] == 0 and 1 <= p["split"] and p["split"] * c["tiles"] <= lim, (c, p)
+        assert p["grid"] == p["split"] * c["tiles"]
+
+
+def test_queue_waves(driver):
+    """All slots with 0 or 1 other trace in flight; with busy >= 2, slots / min(HG_QUEUE_WAVES_DIV, busy + 1)."""
+    exe, _ = driver
+    got = [p["queue_waves"] for p in plans(exe, [case(busy=b) for b in range(13)])]
+    assert got == [5120, 5120] + [5120 // min(QUEUE_WAVES_DIV, b + 1) for b in range(2, 13)]
+    assert got[2] == 1706 and got[7] == got[12] == 640
+
+
+def test_restatement_random(driver):
+    """The header agrees with the restatement of the earlier code on every output field, over seeded random inputs:
+    tile counts 1 .. 2^27 (refusals included), 1 .. 70,000 frames, every option value."""
+    exe, items = driver
+    rng = random.Random(20250607)
+    cases = []
+    for _ in range(4000):
+        tiles = min(1 << 27, max(1, int(2 ** rng.uniform(0, 27.2)) + rng.randint(-1, 1)))
+        cases.append(dict(
+            n_cu=rng.choice([1, 8, 64, 256, 304, rng.randint(1, 512)]), tiles=tiles,
+            W=rng.choice([8, 33, 64, 1920, 2048, 4093]), H=rng.choice([8, 17, 36, 1080, 2048]),
+            stack_depth=rng.randint(2, 64), n_meshes=rng.randint(0, 10), kernel=rng.choice([0, 1, 2, 3, 4, 5, 5, 5]),
+            block=rng.choice([64, 128, 256]), frame_split=rng.choice([0, 0, 0, 1, 2, 3, 16, 64, 70]),
+            wave_units=rng.randint(0, 4), queue_fill=rng.randint(0, 3), descent_t=rng.randint(-1, 20),
+            tile_order_on=rng.randint(0, 1), coalesce=rng.choice([1, 2, 32, 64]), n_ranks=rng.randint(1, 8),
+            debug_mode=rng.choice([0, 0, 0, 0, 1, 5]), max_bounces=rng.choice([1, 8, 250, 251, 1000]),
+            spp=rng.choice([1, 4, 65534, 65535, 70000]),
+            n_frames=rng.choice([1, 2, 8, 9, 63, 64, 65, 128, 129, 130, rng.randint(1, 70000), rng.randint(1, 300)]),
+            busy=rng.randint(0, 12), sv_waves=rng.randint(1, 5)))
+    got = plans(exe, cases)
+    for c, g in zip(cases, got):
+        assert g == restate(c, items), c
+    assert sum(g["status"] != 0 for g in got) > 20 and sum(g.get("first_queue", 0) for g in got) > 100
+
+
+def test_magic_divide(driver):
+    """umulhi(u, magic) >> shift == u / tiles for u < 2^31 (the shift alone when tiles is a power of two): around every
+    multiple of tiles near 0, near 2^31 / 2 and just below 2^31, and at random."""
+    exe, _ = driver
+    rng = random.Random(7)
+    counts = [1, 2, 3, 5, 7, 4049, 4050, 32400, 65536, (1 << 20) - 1] + [rng.randint(1, 1 << 27) for _ in range(200)]
+    text = []
+    for t in counts:
+        us = set(rng.randrange(1 << 31) for _ in range(1000))
+        for base in (0, (1 << 30) // t * t, ((1 << 31) - 1) // t * t):
+            for m in range(-3, 4):
+                us.update(base + m * t + d for d in range(-2, 3))
+        us = sorted(u for u in us if 0 <= u < (1 << 31))
+        text.append(f"divide {t} {len(us)} " + " ".join(map(str, us)) + "\n")
+    lines = run(exe, "".join(text))
+    assert lines == [f"0 {int(t & (t - 1) == 0)}" for t in counts]
+
+
+@pytest.mark.parametrize("W,H", [(33, 17), (64, 36), (1920, 1080)])
+def test_tile_origin_round_trip(driver, W, H):
+    """hg_tile_origin / hg_for_local_pixels (what hg_readback and hg_set_accumulation walk at N > 1) invert
+    hg_pixel_source for N = 1..8: every pixel visited once, by its owner, at its slot; no slot beyond the image."""
+    exe, _ = driver
+    lines = run(exe, "".join(f"tiling {n} {W} {H}\n" for n in range(1, 9)))
+    assert lines == [f"{W * H} 0 0"] * 8
+
+
+def test_event_pair_guard(driver):
+    """A pair held by the guard ends up in exactly one list on every exit path."""
+    exe, _ = driver
+    assert run(exe, "guard\n") == [
+        "-1 free pending",        # returned before a pair was taken
+        "-2 free 7,8 pending",    # returned early with the pair held: back to the free list
+        "0 free pending 7,8",     # handed to a pending list (twice asked, once moved)
+        "0 free 7,8 pending",     # dismissed by hand, not returned again at scope end
+        "0 free 7,8 pending 9,10",  # a second pair: the first goes back, the second is handed on
+    ]
