@@ -118,6 +118,20 @@ public static class HalogenNative
         public uint reserved;
     }
 
+    // hg_denoise_params (24 B): the display denoiser of hg_readback_begin_denoised / hg_denoise_host.  iterations 1..6
+    // (step 1, 2, 4, ...); a sigma <= 0 switches its term off, one that is on lies in [1e-4, 1e4]; sigma_color is the
+    // one at iteration 0 and halves every iteration; flags is reserved (0)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HgDenoiseParams
+    {
+        public int iterations;
+        public float sigma_color;
+        public float sigma_normal;
+        public float sigma_depth;
+        public int demodulate;
+        public uint flags;
+    }
+
     [DllImport(Lib)] public static extern int hg_abi_version();
     [DllImport(Lib)] public static extern int hg_create(int device, out IntPtr ctx);
     [DllImport(Lib)] public static extern void hg_destroy(IntPtr ctx);
@@ -159,6 +173,14 @@ public static class HalogenNative
         IntPtr dHits);
     [DllImport(Lib)] public static extern int hg_camera_rays(IntPtr ctx, ref HgParams p, int frameCount,
         int[] pixelsXY, long n, [Out] HgRay[] rays);
+    // Denoised display: guide images (first-hit normal + distance, albedo + kind) of explicit camera parameters, and
+    // the display readback through the edge-avoiding a-trous filter (ended by hg_readback_end_data); the host twin
+    [DllImport(Lib)] public static extern int hg_update_guides(IntPtr ctx, ref HgParams p, int frameCount);
+    [DllImport(Lib)] public static extern int hg_readback_guides(IntPtr ctx, [Out] float[] guide0, [Out] float[] guide1,
+        UIntPtr nFloatsEach);
+    [DllImport(Lib)] public static extern int hg_readback_begin_denoised(IntPtr ctx, int format, ref HgDenoiseParams p);
+    [DllImport(Lib)] public static extern int hg_denoise_host(float[] rgba, float[] guide0, float[] guide1, int width,
+        int height, ref HgDenoiseParams p, [Out] float[] outRgba);
     [DllImport(Lib)] public static extern long hg_build_blas(float[] vertices, int nVertices, int[] indices, int nTris,
         float[] rootMin, float[] rootMax, int maxHierarchyDepth, [Out] BVHEntry[] outNodes, long maxNodes);
     [DllImport(Lib)] public static extern long hg_build_blas_mt(float[] vertices, int nVertices, int[] indices,

@@ -171,6 +171,13 @@ struct hg_ctx {
     DevBuf rb_image[HG_READBACK_MAX];
     hipEvent_t rb_untiled[HG_READBACK_MAX] = {};
     int rb_next = 0, rb_pending = 0;  // host image the next begin fills; begun readbacks not yet ended (<= rb_depth)
+
+    // Denoised display (hg_update_guides, hg_readback_begin_denoised; kernels in hg_denoise.hip): the guide images
+    // (row-major W x H float4: normal + t, albedo + kind) and the filter's two colour images, all allocated by
+    // hg_update_guides (the context is idle there), so a denoised begin allocates nothing beside a running server.
+    // guides_valid: they belong to this target size and this device scene (hg_resize and a rebuilding upload clear it)
+    DevBuf guide0, guide1, denoise_work[2];
+    bool guides_valid = false;
 };
 
 // Launch the held frames of a context, if any (hg_runtime.hip; every entry point but hg_render calls it first)

@@ -26,6 +26,7 @@
 #include "hg_tiling.h"
 #include "hg_interval.h"
 #include "hg_pack.h"
+#include "hg_atrous.h"
 #include "hg_host_pool.h"
 #include "hg_pair_guard.h"
 #include "hg_plan.h"
@@ -548,7 +549,8 @@ void hg_destroy(hg_ctx* c) {
     for (hg_ctx::TraceLane& L : c->lanes)
         if (L.stream) (void)hipStreamSynchronize(L.stream);
     for (DevBuf* b : {&c->spheres, &c->meshes, &c->materials, &c->nodes, &c->leaves, &c->tris, &c->normals, &c->cube,
-                      &c->acc, &c->counters_dev, &c->spill, &c->lost, &c->query_in, &c->query_out})
+                      &c->acc, &c->counters_dev, &c->spill, &c->lost, &c->query_in, &c->query_out, &c->guide0,
+                      &c->guide1, &c->denoise_work[0], &c->denoise_work[1]})
         release(*b);
     auto destroy_lanes = [c] {
         for (hg_ctx::TraceLane& L : c->lanes) {
@@ -678,6 +680,7 @@ int hg_upload_scene_gen(hg_ctx* c, uint64_t geometry_generation, const HalogenSp
             return HG_OK;
         }
     }
+    c->guides_valid = false;  // the device scene changes: the guide images (hg_update_guides) are another scene's
     // ---- spheres
     std::vector<float4> sph(size_t(n_spheres) * 3);
     for (int i = 0; i < n_spheres; ++i) {
@@ -926,6 +929,7 @@ int hg_resize(hg_ctx* c, int32_t width, int32_t height) {
     if (int rc = set_device(c)) return rc;
     c->W = width;
     c->H = height;
+    c->guides_valid = false;  // (hg_update_guides: the guide images are the old size's)
     return alloc_target(c);
 }
 
@@ -2118,6 +2122,91 @@ int hg_camera_rays(hg_ctx* c, const hg_params* p, int32_t frame_count, const int
     }
     HG_HIP(c, hipStreamSynchronize(c->stream));
     return HG_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Denoised display (hg_update_guides, hg_readback_guides, hg_readback_begin_denoised; kernels in hg_denoise.hip, the
+// filter's arithmetic in hg_atrous.h)
+// ---------------------------------------------------------------------------------------------------------------------
+uint32_t hg_guides_threads(uint32_t n);
+hipError_t hg_launch_guides(const HgKernelParams& kp, uint32_t frame, void* guide0, void* guide1, uint32_t first,
+                            uint32_t n, hipStream_t stream);
+hipError_t hg_launch_denoise(const void* acc, const void* guide0, const void* guide1, void* const work[2], int32_t W,
+                             int32_t H, int32_t tiles_x, const hg_denoise_params& p, hipStream_t stream,
+                             const void** result);
+
+extern "C" {
+
+int hg_update_guides(hg_ctx* c, const hg_params* p, int32_t frame_count) {
+    if (!c) return HG_E_INVALID;
+    if (!p) return fail(c, HG_E_INVALID, "null params");
+    if (!c->has_scene) return fail(c, HG_E_NOSCENE, "hg_upload_scene not called");
+    if (c->W <= 0) return fail(c, HG_E_NOTARGET, "hg_resize not called");
+    if (!(p->screenParameters.x == float(c->W) && p->screenParameters.y == float(c->H)))
+        return fail(c, HG_E_INVALID, "screenParameters (%g,%g) are not the target's size %dx%d", p->screenParameters.x,
+                    p->screenParameters.y, c->W, c->H);
+    if (int rc = query_begin(c)) return rc;
+    // the context is idle: the four images may move
+    c->guides_valid = false;
+    const size_t pixels = size_t(c->W) * size_t(c->H);
+    for (DevBuf* b : {&c->guide0, &c->guide1, &c->denoise_work[0], &c->denoise_work[1]})
+        if (int rc = ensure(c, *b, pixels * sizeof(float4))) return rc;
+    // the closest-hit query's parameter block (the whole uploaded scene, far = +inf) with the caller's camera
+    HgKernelParams kp;
+    if (int rc = query_params(c, hg_guides_threads(uint32_t(std::min<size_t>(pixels, size_t(kQueryChunk)))), kp)) return rc;
+    const float far_ = kp.far_;
+    set_camera(kp, *p);
+    kp.far_ = far_;
+    for (size_t at = 0; at < pixels; at += size_t(kQueryChunk)) {  // in stream order: the launches share the spill buffer
+        const uint32_t m = uint32_t(std::min(pixels - at, size_t(kQueryChunk)));
+        HG_HIP(c, hg_launch_guides(kp, uint32_t(frame_count), c->guide0.p, c->guide1.p, uint32_t(at), m, c->stream));
+    }
+    HG_HIP(c, hipStreamSynchronize(c->stream));
+    c->guides_valid = true;
+    return HG_OK;
+}
+
+int hg_readback_guides(hg_ctx* c, float* guide0, float* guide1, size_t n_floats_each) {
+    if (!c) return HG_E_INVALID;
+    if (c->W <= 0) return fail(c, HG_E_NOTARGET, "hg_resize not called");
+    if (!c->guides_valid) return fail(c, HG_E_INVALID, "no guide images for this scene and target: call hg_update_guides");
+    const size_t bytes = size_t(c->W) * size_t(c->H) * sizeof(float4);
+    if (n_floats_each * sizeof(float) < bytes) return fail(c, HG_E_INVALID, "guide buffer too small");
+    if (int rc = set_device(c)) return rc;
+    if (guide0) HG_HIP(c, hipMemcpyAsync(guide0, c->guide0.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (guide1) HG_HIP(c, hipMemcpyAsync(guide1, c->guide1.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HG_HIP(c, hipStreamSynchronize(c->stream));
+    return HG_OK;
+}
+
+int hg_readback_begin_denoised(hg_ctx* c, int32_t format, const hg_denoise_params* p) {
+    if (!c) return HG_E_INVALID;
+    if (!p) return fail(c, HG_E_INVALID, "null denoise params");
+    if (!hg_atrous_params_ok(*p))
+        return fail(c, HG_E_INVALID,
+                    "bad denoise params: iterations %d (1..%d), sigmas %g %g %g (off, or in [1e-4, 1e4]), demodulate %d, "
+                    "flags %u", p->iterations, HG_ATROUS_MAX_ITERATIONS, p->sigma_color, p->sigma_normal, p->sigma_depth,
+                    p->demodulate, p->flags);
+    if (int rc = hg_ctx_flush(c)) return rc;
+    if (c->W <= 0) return fail(c, HG_E_NOTARGET, "hg_resize not called");
+    if (!display_bpp(format)) return fail(c, HG_E_INVALID, "unknown display format %d", format);
+    if (c->n_ranks > 1)
+        return fail(c, HG_E_UNSUPPORTED, "denoised display of a tiled context (rank %d of %d): a rank's share has no "
+                    "neighbours", c->rank, c->n_ranks);
+    if (int64_t(c->W) * c->H > HG_ATROUS_MAX_PIXELS)
+        return fail(c, HG_E_UNSUPPORTED, "denoised display of more than 2^28 pixels (%dx%d)", c->W, c->H);
+    if (!c->guides_valid) return fail(c, HG_E_INVALID, "no guide images for this scene and target: call hg_update_guides");
+    if (c->rb_pending >= c->rb_depth)
+        return fail(c, HG_E_INVALID, "%d readbacks outstanding (HG_OPT_READBACK_DEPTH): call hg_readback_end first",
+                    c->rb_pending);
+    if (int rc = set_device(c)) return rc;
+    // on the context stream, after every frame rendered so far (the server keeps tracing: nothing here waits)
+    void* const work[2] = {c->denoise_work[0].p, c->denoise_work[1].p};
+    const void* denoised = nullptr;
+    HG_HIP(c, hg_launch_denoise(c->acc.p, c->guide0.p, c->guide1.p, work, c->W, c->H, c->tiles_x, *p, c->stream, &denoised));
+    return hg_ctx_display_begin(c, denoised, format);
 }
 
 }  // extern "C"

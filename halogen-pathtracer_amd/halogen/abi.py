@@ -111,6 +111,15 @@ RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("kind", np.uint32), ("object", np.
                           ("u", np.float32), ("v", np.float32), ("material", np.uint32), ("orientation", np.float32),
                           ("normal", np.float32, 3), ("reserved", np.uint32)])
 HG_HIT_NONE, HG_HIT_MESH, HG_HIT_SPHERE = 0, 1, 2
+
+
+class DenoiseParams(C.Structure):  # hg_denoise_params, 24 B (include/halogen_abi.h, csrc/hg_atrous.h)
+    """The display denoiser's settings: 1..6 a-trous iterations (step 1, 2, 4, ...), the three edge-stopping sigmas
+    (<= 0: term off; the colour sigma is the one at iteration 0 and halves every iteration) and albedo demodulation."""
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("demodulate", C.c_int32), ("flags", C.c_uint32)]
+
+
 HG_RAYS_CLOSEST, HG_RAYS_ANY = 0, 1
 RAY_MODES = {"closest": HG_RAYS_CLOSEST, "any": HG_RAYS_ANY}
 
@@ -145,7 +154,8 @@ EXPORTS = [
     "hg_set_params", "hg_resize", "hg_set_tiling", "hg_clear_accumulation", "hg_render", "hg_synchronize",
     "hg_readback", "hg_readback_begin", "hg_readback_end", "hg_readback_begin_format", "hg_readback_end_data",
     "hg_pack_display", "hg_set_accumulation", "hg_copy_tiles_device", "hg_local_tile_count", "hg_get_counters", "hg_reset_counters",
-    "hg_set_option", "hg_selftest", "hg_trace_rays", "hg_trace_rays_device", "hg_camera_rays", "hg_build_blas", "hg_build_blas_mt", "hg_build_blas_sah", "hg_unity_bounds", "hg_pack_triangles",
+    "hg_set_option", "hg_selftest", "hg_trace_rays", "hg_trace_rays_device", "hg_camera_rays",
+    "hg_update_guides", "hg_readback_guides", "hg_readback_begin_denoised", "hg_denoise_host", "hg_build_blas", "hg_build_blas_mt", "hg_build_blas_sah", "hg_unity_bounds", "hg_pack_triangles",
     "hg_comm_unique_id", "hg_comm_init_rank", "hg_comm_init_all", "hg_comm_gather", "hg_comm_synchronize",
     "hg_comm_readback", "hg_comm_readback_begin", "hg_comm_readback_end", "hg_comm_set_timeout_ms", "hg_comm_transport", "hg_comm_last_error", "hg_comm_destroy",
     "hg_comm_assemble_host",
@@ -200,6 +210,10 @@ def lib() -> C.CDLL:
         "hg_trace_rays": (C.c_int, [P, P, i64, i32, P]),
         "hg_trace_rays_device": (C.c_int, [P, P, i64, i32, P]),
         "hg_camera_rays": (C.c_int, [P, C.POINTER(HgParams), i32, P, i64, P]),
+        "hg_update_guides": (C.c_int, [P, C.POINTER(HgParams), i32]),
+        "hg_readback_guides": (C.c_int, [P, f32p, f32p, sz]),
+        "hg_readback_begin_denoised": (C.c_int, [P, i32, C.POINTER(DenoiseParams)]),
+        "hg_denoise_host": (C.c_int, [f32p, f32p, f32p, i32, i32, C.POINTER(DenoiseParams), f32p]),
         "hg_build_blas": (i64, [P, i32, P, i32, f32p, f32p, i32, P, i64]),
         "hg_build_blas_mt": (i64, [P, i32, P, i32, f32p, f32p, i32, P, i64, i32]),
         "hg_build_blas_sah": (i64, [P, i32, P, i32, i32, i32, P, i64]),
@@ -277,6 +291,7 @@ class Context:
             raise HalogenError(f"hg_create(device={device}) failed with {rc} (no usable HIP device?)")
         self._h = h
         self.device = device
+        self._size = None  # (w, h) of the last resize (guides())
 
     def _check(self, rc: int, what: str):
         if rc != HG_OK:
@@ -318,6 +333,7 @@ class Context:
 
     def resize(self, w: int, h: int) -> None:
         self._check(lib().hg_resize(self._h, w, h), "hg_resize")
+        self._size = (int(w), int(h))
 
     def set_tiling(self, rank: int, n_ranks: int) -> None:
         self._check(lib().hg_set_tiling(self._h, rank, n_ranks), "hg_set_tiling")
@@ -337,10 +353,14 @@ class Context:
         self._check(lib().hg_readback(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "hg_readback")
         return out
 
-    def readback_begin(self, fmt: int | None = None) -> None:
+    def readback_begin(self, fmt: int | None = None, denoise: "DenoiseParams | None" = None) -> None:
         """hg_readback_begin(_format): enqueue the display readback of every frame rendered so far (at most
-        HG_OPT_READBACK_DEPTH outstanding), as RGBA32F or another HG_DISPLAY_* format."""
-        if fmt is None:
+        HG_OPT_READBACK_DEPTH outstanding), as RGBA32F or another HG_DISPLAY_* format.  denoise: the image goes through
+        the edge-avoiding a-trous filter first (hg_readback_begin_denoised; needs update_guides)."""
+        if denoise is not None:
+            self._check(lib().hg_readback_begin_denoised(self._h, HG_DISPLAY_RGBA32F if fmt is None else int(fmt),
+                                                         C.byref(denoise)), "hg_readback_begin_denoised")
+        elif fmt is None:
             self._check(lib().hg_readback_begin(self._h), "hg_readback_begin")
         else:
             self._check(lib().hg_readback_begin_format(self._h, int(fmt)), "hg_readback_begin_format")
@@ -418,6 +438,26 @@ class Context:
         self._check(lib().hg_camera_rays(self._h, C.byref(params), int(frame_count), _ptr(px), px.shape[0], _ptr(rays)),
                     "hg_camera_rays")
         return rays
+
+    # --- denoised display (hg_update_guides, hg_readback_guides; readback_begin(denoise=...)) -------------------------
+    def update_guides(self, params: HgParams, frame_count: int) -> None:
+        """Trace the guide images (first-hit normal + distance, albedo + kind) of the camera rays frame `frame_count`
+        traces under `params` (explicit, as in camera_rays); filterRadius = focalConeAngle = 0 gives guides that do not
+        change from frame to frame."""
+        self._check(lib().hg_update_guides(self._h, C.byref(params), int(frame_count)), "hg_update_guides")
+
+    def guides(self) -> tuple[np.ndarray, np.ndarray]:
+        """The guide images of the last update_guides: two (h, w, 4) float32 arrays, (normal.xyz, t) with t = +inf for
+        a miss and (albedo.rgb, kind as 0.0 / 1.0 / 2.0)."""
+        if self._size is None:
+            raise HalogenError("guides: resize not called", HG_E_NOTARGET)
+        w, h = self._size
+        g0 = np.zeros((h, w, 4), dtype=np.float32)
+        g1 = np.zeros((h, w, 4), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(lib().hg_readback_guides(self._h, g0.ctypes.data_as(fp), g1.ctypes.data_as(fp), g0.size),
+                    "hg_readback_guides")
+        return g0, g1
 
     def selftest(self, test: int = HG_SELFTEST_RCP) -> tuple[int, int]:
         """(mismatches, inputs tested) of a device arithmetic self-test."""
@@ -531,6 +571,25 @@ def assemble_host(slabs: np.ndarray, width: int, height: int, n_ranks: int) -> n
                                      out.size)
     if rc != HG_OK:
         raise HalogenError(f"hg_comm_assemble_host failed ({rc}): slabs {s.shape} for {width}x{height}, {n_ranks} ranks")
+    return out
+
+
+def denoise_host(rgba: np.ndarray, guide0: np.ndarray, guide1: np.ndarray, params: DenoiseParams) -> np.ndarray:
+    """hg_denoise_host: the display denoiser on the host (no device work), bit-identical to
+    Context.readback_begin(denoise=params).  rgba, guide0, guide1: (h, w, 4) float32; returns (h, w, 4) float32."""
+    img = np.ascontiguousarray(rgba, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError(f"denoise_host: rgba must be (h, w, 4), got {img.shape}")
+    g0 = np.ascontiguousarray(guide0, dtype=np.float32)
+    g1 = np.ascontiguousarray(guide1, dtype=np.float32)
+    if g0.shape != img.shape or g1.shape != img.shape:
+        raise ValueError(f"denoise_host: guides {g0.shape} {g1.shape} do not match the image {img.shape}")
+    out = np.empty_like(img)
+    fp = C.POINTER(C.c_float)
+    rc = lib().hg_denoise_host(img.ctypes.data_as(fp), g0.ctypes.data_as(fp), g1.ctypes.data_as(fp), img.shape[1],
+                               img.shape[0], C.byref(params), out.ctypes.data_as(fp))
+    if rc != HG_OK:
+        raise HalogenError(f"hg_denoise_host failed ({rc}): bad size or parameters", rc)
     return out
 
 

@@ -139,6 +139,23 @@ def clamp_settings(st: HalogenSettings) -> dict:
     return d
 
 
+@dataclass
+class DenoiseSettings:
+    """The display denoiser of set_display(denoise=...): a preview filter for the first tens of accumulated frames (an
+    edge-avoiding a-trous filter over colour, first-hit normal and distance; include/halogen_abi.h).  The colour sigma
+    shrinks with the noise: sigma_color = sigma_color_1 / sqrt(frames accumulated).  A sigma <= 0 switches its term off."""
+    iterations: int = 3
+    sigma_color_1: float = 8.0
+    sigma_normal: float = 0.3
+    sigma_depth: float = 0.0
+    demodulate: bool = True
+
+    def params(self, frames: int) -> abi.DenoiseParams:
+        sc = self.sigma_color_1 / math.sqrt(max(1, int(frames))) if self.sigma_color_1 > 0 else 0.0
+        return abi.DenoiseParams(int(self.iterations), float(sc), float(self.sigma_normal), float(self.sigma_depth),
+                                 1 if self.demodulate else 0, 0)
+
+
 class HalogenRenderPass:
     """Progressive path tracing of a `halogen.scene.Scene` on one GPU (or one rank's tiles)."""
 
@@ -168,12 +185,16 @@ class HalogenRenderPass:
         self.display_latency = 0
         self._display_pending = 0
         self._display_resync = False
+        # set_display(denoise=...): the guide images follow the camera and the scene, not the frames (stable rays)
+        self.display_denoise = None
+        self._guides_dirty = True
 
     # ---- RP:237-268 ----------------------------------------------------------------------------
     def OnCameraSetup(self, width: int, height: int):
         res = (int(width), int(height))
         if res != self._prior_resolution:
             self.ctx.resize(*res)
+            self._guides_dirty = True
             self._display_pending = 0  # hg_resize drops the display readbacks in flight
             self.ClearAccumulation()
         self._prior_resolution = res
@@ -202,6 +223,7 @@ class HalogenRenderPass:
                 self._geometry = (sig, self._geometry[1] + 1)
             generation = self._geometry[1]
         self.ctx.upload_scene(packed, generation)
+        self._guides_dirty = True
         self._scene_counts = (len(packed.spheres), len(packed.meshes))
         cube = self.settings.environmentCubemap
         if self.s["UseEnvironmentCubemap"] and not self._cubemap_uploaded:
@@ -216,6 +238,7 @@ class HalogenRenderPass:
         self.OnCameraSetup(camera.pixelWidth, camera.pixelHeight)
         pose = camera.pose()
         if camera_moved(self._prior_pose, pose):
+            self._guides_dirty = True
             self.ClearAccumulation()
         if self.FrameCount > 1 and not self.s["Accumulate"]:
             self.ClearAccumulation()
@@ -224,6 +247,7 @@ class HalogenRenderPass:
         if self.ObjectBuffersDirty:
             self.UpdateObjectBuffers(scene)
             self.ObjectBuffersDirty = False
+        self._refresh_guides()
         if not self.s["UnlimitedSampling"] and self.FrameCount > self.s["MaxAccumulatedFrames"]:
             return  # rendering done: the reference only re-blits the finished image
         if not self.s["UnlimitedSampling"]:
@@ -238,19 +262,39 @@ class HalogenRenderPass:
             self.FrameCount += n_frames
 
     # ---- the per-frame display (RP:343-347), pipelined, as the C# and C++ passes do it ---------------------------------
-    def set_display(self, fmt: int = abi.HG_DISPLAY_R11G11B10F, latency: int = 0):
+    def set_display(self, fmt: int = abi.HG_DISPLAY_R11G11B10F, latency: int = 0,
+                    denoise: DenoiseSettings | None = None):
         """Display format (abi.HG_DISPLAY_*) and how many frames the shown image may lag (0 .. HG_READBACK_MAX - 1 =
-        15; 0, the default, shows each frame before the next is traced, as the reference does)."""
+        15; 0, the default, shows each frame before the next is traced, as the reference does).  denoise: show the
+        accumulation through the preview denoiser (DenoiseSettings; not in the reference, not with tiling); None, the
+        default, shows it as it is."""
         if not 0 <= latency < abi.HG_READBACK_MAX:
             raise ValueError("display latency out of range")
         self.flush_display()
         self.ctx.set_option(abi.HG_OPT_READBACK_DEPTH, latency + 1)
         self.display_format, self.display_latency = int(fmt), int(latency)
+        self.display_denoise = denoise
+
+    def _refresh_guides(self):
+        """The denoiser's guide images, traced with the stable rays (no jitter, no aperture, frame 1) when the target
+        size, the scene buffers or the camera changed since the last ones, and at no other time."""
+        if self.display_denoise is None or not self._guides_dirty or self._last_camera is None:
+            return
+        p = make_params(self.s, self._last_camera, 1, *self._scene_counts, self.s["UseEnvironmentCubemap"])
+        p.filterRadius = 0.0
+        p.focalConeAngle = 0.0
+        self.ctx.update_guides(p, 1)
+        self._guides_dirty = False
 
     def display(self):
         """Enqueue the display readback of every frame rendered so far; return the image of `display_latency` calls ago
         (None while the pipeline fills): (h, w) uint32 R11G11B10F, (h, w, 4) float16 or float32."""
-        self.ctx.readback_begin(self.display_format)
+        if self.display_denoise is not None:
+            self._refresh_guides()  # (set_display after the last Execute)
+            frames = self.FrameCount - 1 if self.s["Accumulate"] else 1
+            self.ctx.readback_begin(self.display_format, denoise=self.display_denoise.params(frames))
+        else:
+            self.ctx.readback_begin(self.display_format)
         self._display_pending += 1
         if self._display_resync:  # the first frame after a clear: shown at once
             self._display_resync = False

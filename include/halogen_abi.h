@@ -454,6 +454,63 @@ int hg_camera_rays(hg_ctx* ctx, const hg_params* params, int32_t frame_count, co
                    hg_ray* rays);
 
 /* ----------------------------------------------------------------------------------------------
+ * Denoised display (not in the reference, which shows the raw accumulation): per-pixel guide buffers and an
+ * edge-avoiding a-trous filter (Dammertz et al. 2010) between the accumulation target and the display readback.  A
+ * PREVIEW filter for the first tens of accumulated frames (a moving camera's 1-sample frames, the first seconds after
+ * it stops): its colour sigma must shrink as 1/sqrt(frames), and on a mostly converged image it only adds bias.
+ *
+ * Guides.  hg_update_guides traces one closest-hit ray for every pixel of the target, exactly the ray
+ * hg_camera_rays(params, frame_count, pixel) hands out, answered as hg_trace_rays(HG_RAYS_CLOSEST) answers it, and
+ * keeps two row-major width x height float4 images on the context (also the normal / depth / albedo outputs an external
+ * denoiser asks for):
+ *   guide0 = (normal.xyz, t)                 a miss: (0, 0, 0, +inf)
+ *   guide1 = (albedo.rgb, kind as a float)   albedo = materials[hit.material].albedo.xyz; a miss: (1, 1, 1, 0)
+ * `params` is required and explicit, as in hg_camera_rays (the context's own parameters are neither read nor changed);
+ * its screenParameters must be the target's size (else HG_E_INVALID).  A caller who wants the guides of the very ray a
+ * 1-sample frame traced passes that frame's parameters; filterRadius = 0 and focalConeAngle = 0 make the jitter and the
+ * aperture exactly zero, so the guides do not change from frame to frame.  Needs an uploaded scene (HG_E_NOSCENE) and
+ * a target (HG_E_NOTARGET).  Ordering as the ray queries: launches the held frames, stops a render server, runs on the
+ * context stream, returns complete; never touches the accumulation, FrameCount, hg_counters, the options or the tiling
+ * (a tiled context computes the guides of the whole image).  hg_resize and an hg_upload_scene[_gen] that rebuilt anything (not a skipped one) mark the guides stale.  hg_readback_guides copies them out (width*height*4
+ * floats each; either pointer may be NULL); stale or missing guides are HG_E_INVALID.
+ *
+ * The filter (csrc/hg_atrous.h has the exact arithmetic, shared by the device and hg_denoise_host):
+ *   demodulation (demodulate = 1): a = max(albedo, 1e-3) per channel, c = C.rgb / a;
+ *   iteration i = 0 .. iterations-1, step s = 1 << i, sigma_c = sigma_color * 2^-i: for pixel p the 5x5 taps
+ *     q = p + s * (dx, dy) inside the image (dy outer, dx inner), h = k[|dy|] * k[|dx|], k = {3/8, 1/4, 1/16},
+ *     e = |c_p - c_q|^2 / sigma_c^2 + |n_p - n_q|^2 / sigma_normal^2 + (t_p - t_q)^2 / sigma_depth^2 over the terms
+ *     that are on (the depth term only where t_p != t_q; a miss against a hit: e = +inf, whatever terms are on),
+ *     w = h * exp(-e), c'_p = sum(w * c_q) / sum(w);
+ *   output rgb = c * a when demodulated, alpha = the input's.
+ * A sigma <= 0 switches its term off; a sigma that is on lies in [1e-4, 1e4].  iterations outside 1..6, a sigma out of
+ * range or NaN, demodulate other than 0 / 1, or flags != 0 is HG_E_INVALID.
+ *
+ * hg_readback_begin_denoised is hg_readback_begin_format with the filter in between, ended by hg_readback_end_data:
+ * on the context stream the accumulator is untiled (and demodulated) into a context-owned image, the iterations run
+ * between two such images, and the result goes through the display conversion, ring and copy of the plain readback
+ * (same HG_OPT_READBACK_DEPTH / HG_OPT_READBACK_STREAM; plain and denoised begins may be mixed and end in begin order).
+ * Like hg_readback_begin_format it launches the held frames, does NOT stop a render server or wait for the device, and
+ * returns HG_E_FRAME_LOST in the same cases.  It never writes the accumulator.  Stale or missing guides are
+ * HG_E_INVALID (call hg_update_guides); a tiled context (n_ranks > 1) is HG_E_UNSUPPORTED: a rank's share has no
+ * neighbours; so is a target of more than 2^28 pixels.
+ * hg_denoise_host is the host twin (no device work): the same filter over row-major width*height*4 float images,
+ * bit-identical to the device's; out_rgba must not alias the inputs.
+ * -------------------------------------------------------------------------------------------- */
+typedef struct hg_denoise_params {
+    int32_t iterations;      /* 1..6: step 1, 2, 4, ... */
+    float sigma_color;       /* at iteration 0; halves every iteration.  <= 0: term off */
+    float sigma_normal;      /* <= 0: term off */
+    float sigma_depth;       /* <= 0: term off */
+    int32_t demodulate;      /* 0 / 1 */
+    uint32_t flags;          /* reserved, 0 */
+} hg_denoise_params;
+int hg_update_guides(hg_ctx* ctx, const hg_params* params, int32_t frame_count);
+int hg_readback_guides(hg_ctx* ctx, float* guide0, float* guide1, size_t n_floats_each);
+int hg_readback_begin_denoised(hg_ctx* ctx, int32_t format, const hg_denoise_params* p);
+int hg_denoise_host(const float* rgba, const float* guide0, const float* guide1, int32_t width, int32_t height,
+                    const hg_denoise_params* p, float* out_rgba);
+
+/* ----------------------------------------------------------------------------------------------
  * Multi-GPU framebuffer gather (not in the reference, which is single-GPU).
  * Every rank renders the 8x8 tiles t % n_ranks == rank of the same image (hg_set_tiling) with its own context, on
  * its own GPU; the only exchange is one gather of the ranks' accumulated tiles to the root, which assembles the
