@@ -1,16 +1,20 @@
 // hg_layout.h — device-side data layout of the Halogen scene in HBM (private to libhalogen_hip.so).
 //
 // The ABI structs (include/halogen_abi.h) are the reference's AoS C# layouts.  hg_upload_scene repacks
-// them once into the layout below, chosen for the gfx950 traversal loop:
+// them once (hg_scene_pack.h) into the layout below, chosen for the gfx950 traversal loop:
 //
-//   node records   64 B per BLAS entry, CHILD-PAIR form: record g holds the boxes of g's two children and
-//                  their node refs, so popping an inner node costs exactly one 64-B record fetch (4 x
-//                  dwordx4) and the reference's re-read of the popped node (HalgoenCompute.compute:405)
-//                  disappears.  Records of leaf entries are never read.
-//   leaf table     8 B per BLAS entry: (global first triangle, triangle count) — read only for leaves.
-//   node ref       uint32: bit 31 = leaf, bits 0..30 = global BLAS index (= accelerationBufferOffset +
-//                  mesh-relative index).  Decided at upload from triangleCount, so the kernel never has to
-//                  read a node to know what it is.
+//   node records   64 B per INNER BLAS entry, CHILD-PAIR form: a record holds the boxes of the entry's two
+//                  children and their node refs, so popping an inner node costs exactly one 64-B record fetch
+//                  (4 x dwordx4) and the reference's re-read of the popped node (HalgoenCompute.compute:405)
+//                  disappears.  Leaf entries have no record.  Records are numbered in depth-first pre-order of
+//                  sibling pairs: two inner siblings sit at records 2k and 2k + 1 (one 128-B line; a zero pad
+//                  record is inserted where the pair would start odd) and a subtree's records are contiguous.
+//   node ref       uint32, decided at upload from triangleCount, so the kernel never has to read a node to
+//                  know what it is.  Bit 31 clear: the record number of an inner entry.  Bit 31 set: a leaf;
+//                  a leaf of 1..15 triangles whose first triangle is below 2^27 is INLINE, HG_LEAF_BIT |
+//                  count << 27 | global first triangle (no memory access to find its triangles; never equal
+//                  to HG_NONE); any other leaf has count bits 0 and indexes the leaf table.
+//   leaf table     the escape for larger leaves, 8 B each: (global first triangle, triangle count).
 //   triangles      36 B per triangle, packed (v0.xyz, e1.xyz, e2.xyz), where e1 = v1 - v0 and e2 = v2 - v0 are the
 //                  reference's own first two subtractions (:312-313) done once on the host with the same IEEE
 //                  operation; a leaf's triangles sit on 2-3 cache lines.
@@ -38,7 +42,7 @@ struct alignas(16) HgDevMesh {
     uint32_t material;
     uint32_t cullable;  // 1: the root is an inner node and cull_* hold its children's padded world boxes
     // World-space boxes of the root's two children, padded far beyond every float rounding of the reference's
-    // local-space test (hg_runtime.hip: mesh_cull_boxes).  If a ray certainly misses both (or meets them only
+    // local-space test (hg_scene_pack.h: mesh_cull_boxes).  If a ray certainly misses both (or meets them only
     // beyond its current closest hit), the reference's traversal of this mesh would test exactly those two
     // boxes, push nothing and find nothing — so the mesh is skipped and only its 2 AABB tests are counted.
     float4 cull_a_lo, cull_a_hi, cull_b_lo, cull_b_hi;

@@ -27,7 +27,7 @@
 #include "hg_interval.h"
 #include "hg_pack.h"
 #include "hg_atrous.h"
-#include "hg_host_pool.h"
+#include "hg_scene_pack.h"
 #include "hg_pair_guard.h"
 #include "hg_plan.h"
 
@@ -49,8 +49,14 @@ namespace {
 
 using EventPair = std::pair<hipEvent_t, hipEvent_t>;
 using EventGuard = HgPairGuard<EventPair>;  // a timing pair that goes back to free_events unless handed on
-constexpr uint32_t kMaxStack = 64;  // LDS stack entries per lane; BLAS depth must be <= kMaxStack - 2
-constexpr int kHostThreads = 16;    // host threads of hg_upload_scene's compare / repack (the GPU box's CPU share)
+
+// hg_scene_pack.h packs with HIP's vector types here and with its own plain structs under g++ (its tests): the same bytes
+#ifdef HG_VECTOR_SHIM
+#error "hg_scene_pack.h defined its float4 / uint2 shim in a HIP translation unit"
+#endif
+static_assert(sizeof(float4) == HG_FLOAT4_BYTES && alignof(float4) == HG_FLOAT4_BYTES, "float4 differs from the shim");
+static_assert(sizeof(uint2) == HG_UINT2_BYTES && alignof(uint2) == HG_UINT2_BYTES, "uint2 differs from the shim");
+static_assert(sizeof(HgDevMesh) == 144 && alignof(HgDevMesh) == 16, "HgDevMesh is 144 B (hg_layout.h)");
 
 }  // namespace
 
@@ -93,146 +99,6 @@ int upload(hg_ctx* c, DevBuf& b, const void* src, size_t bytes) {
     }
     if (bytes) HG_HIP(c, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
     return HG_OK;
-}
-
-float4 f4(float x, float y, float z, float w) { return make_float4(x, y, z, w); }
-float bits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-float bits(int32_t i) { float f; std::memcpy(&f, &i, 4); return f; }
-
-// Padded world-space boxes of a mesh root's two children (for the exact mesh skip, hg_device.h mesh_live_mask).
-// The local box corners go through the double-precision inverse of the float worldToLocal the kernel uses;
-// the pad (1e-3 of the box size + 1e-4 of the coordinate magnitude + 1e-5) exceeds by orders of magnitude
-// the float rounding of the reference's local-space slab test (~1e-7 relative), so "misses the padded box"
-// implies "the reference's ray_AABB_test returns INF (or a tEntry beyond the closest hit)".
-bool invert4(const double a[16], double out[16]) {
-    double inv[16];
-    inv[0] = a[5] * a[10] * a[15] - a[5] * a[11] * a[14] - a[9] * a[6] * a[15] + a[9] * a[7] * a[14] +
-             a[13] * a[6] * a[11] - a[13] * a[7] * a[10];
-    inv[4] = -a[4] * a[10] * a[15] + a[4] * a[11] * a[14] + a[8] * a[6] * a[15] - a[8] * a[7] * a[14] -
-             a[12] * a[6] * a[11] + a[12] * a[7] * a[10];
-    inv[8] = a[4] * a[9] * a[15] - a[4] * a[11] * a[13] - a[8] * a[5] * a[15] + a[8] * a[7] * a[13] +
-             a[12] * a[5] * a[11] - a[12] * a[7] * a[9];
-    inv[12] = -a[4] * a[9] * a[14] + a[4] * a[10] * a[13] + a[8] * a[5] * a[14] - a[8] * a[6] * a[13] -
-              a[12] * a[5] * a[10] + a[12] * a[6] * a[9];
-    inv[1] = -a[1] * a[10] * a[15] + a[1] * a[11] * a[14] + a[9] * a[2] * a[15] - a[9] * a[3] * a[14] -
-             a[13] * a[2] * a[11] + a[13] * a[3] * a[10];
-    inv[5] = a[0] * a[10] * a[15] - a[0] * a[11] * a[14] - a[8] * a[2] * a[15] + a[8] * a[3] * a[14] +
-             a[12] * a[2] * a[11] - a[12] * a[3] * a[10];
-    inv[9] = -a[0] * a[9] * a[15] + a[0] * a[11] * a[13] + a[8] * a[1] * a[15] - a[8] * a[3] * a[13] -
-             a[12] * a[1] * a[11] + a[12] * a[3] * a[9];
-    inv[13] = a[0] * a[9] * a[14] - a[0] * a[10] * a[13] - a[8] * a[1] * a[14] + a[8] * a[2] * a[13] +
-              a[12] * a[1] * a[10] - a[12] * a[2] * a[9];
-    inv[2] = a[1] * a[6] * a[15] - a[1] * a[7] * a[14] - a[5] * a[2] * a[15] + a[5] * a[3] * a[14] +
-             a[13] * a[2] * a[7] - a[13] * a[3] * a[6];
-    inv[6] = -a[0] * a[6] * a[15] + a[0] * a[7] * a[14] + a[4] * a[2] * a[15] - a[4] * a[3] * a[14] -
-             a[12] * a[2] * a[7] + a[12] * a[3] * a[6];
-    inv[10] = a[0] * a[5] * a[15] - a[0] * a[7] * a[13] - a[4] * a[1] * a[15] + a[4] * a[3] * a[13] +
-              a[12] * a[1] * a[7] - a[12] * a[3] * a[5];
-    inv[14] = -a[0] * a[5] * a[14] + a[0] * a[6] * a[13] + a[4] * a[1] * a[14] - a[4] * a[2] * a[13] -
-              a[12] * a[1] * a[6] + a[12] * a[2] * a[5];
-    inv[3] = -a[1] * a[6] * a[11] + a[1] * a[7] * a[10] + a[5] * a[2] * a[11] - a[5] * a[3] * a[10] -
-             a[9] * a[2] * a[7] + a[9] * a[3] * a[6];
-    inv[7] = a[0] * a[6] * a[11] - a[0] * a[7] * a[10] - a[4] * a[2] * a[11] + a[4] * a[3] * a[10] +
-             a[8] * a[2] * a[7] - a[8] * a[3] * a[6];
-    inv[11] = -a[0] * a[5] * a[11] + a[0] * a[7] * a[9] + a[4] * a[1] * a[11] - a[4] * a[3] * a[9] -
-              a[8] * a[1] * a[7] + a[8] * a[3] * a[5];
-    inv[15] = a[0] * a[5] * a[10] - a[0] * a[6] * a[9] - a[4] * a[1] * a[10] + a[4] * a[2] * a[9] +
-              a[8] * a[1] * a[6] - a[8] * a[2] * a[5];
-    const double det = a[0] * inv[0] + a[1] * inv[4] + a[2] * inv[8] + a[3] * inv[12];
-    if (!(std::fabs(det) > 1e-30) || !std::isfinite(det)) return false;
-    for (int i = 0; i < 16; ++i) out[i] = inv[i] / det;
-    return true;
-}
-
-bool world_box(const double l2w[16], const BVHEntry& e, float4& lo, float4& hi) {
-    const float c[2][3] = {{e.boundingCornerA.x, e.boundingCornerA.y, e.boundingCornerA.z},
-                           {e.boundingCornerB.x, e.boundingCornerB.y, e.boundingCornerB.z}};
-    double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
-    for (int k = 0; k < 8; ++k) {
-        const double p[3] = {c[k & 1][0], c[(k >> 1) & 1][1], c[(k >> 2) & 1][2]};
-        for (int r = 0; r < 3; ++r) {  // column-major: M(r,col) = l2w[col*4 + r]
-            const double w = l2w[r] * p[0] + l2w[4 + r] * p[1] + l2w[8 + r] * p[2] + l2w[12 + r];
-            if (!std::isfinite(w)) return false;
-            mn[r] = std::min(mn[r], w);
-            mx[r] = std::max(mx[r], w);
-        }
-    }
-    double size = 0.0, mag = 0.0;
-    for (int r = 0; r < 3; ++r) {
-        size = std::max(size, mx[r] - mn[r]);
-        mag = std::max({mag, std::fabs(mn[r]), std::fabs(mx[r])});
-    }
-    const double pad = 1e-3 * size + 1e-4 * mag + 1e-5;
-    lo = make_float4(float(mn[0] - pad), float(mn[1] - pad), float(mn[2] - pad), 0.0f);
-    hi = make_float4(float(mx[0] + pad), float(mx[1] + pad), float(mx[2] + pad), 0.0f);
-    return true;
-}
-
-bool mesh_cull_boxes(const hg_mat4& w2l, const BVHEntry& A, const BVHEntry& B, HgDevMesh& dm) {
-    double a[16], l2w[16];
-    for (int i = 0; i < 16; ++i) a[i] = w2l.m[i];
-    if (!invert4(a, l2w)) return false;
-    return world_box(l2w, A, dm.cull_a_lo, dm.cull_a_hi) && world_box(l2w, B, dm.cull_b_lo, dm.cull_b_hi);
-}
-
-// A mesh record's exact-cull boxes (its root's two children in world space) and cullable flag, from its matrix; all
-// zero when not cullable, so a partial re-upload leaves no field of the previous matrix behind
-void set_cull_boxes(const HalogenMeshData& m, const BVHEntry* blas, HgDevMesh& dm) {
-    dm.cullable = 0;
-    dm.cull_a_lo = dm.cull_a_hi = dm.cull_b_lo = dm.cull_b_hi = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    const uint32_t off = m.accelerationBufferOffset;
-    if (blas[off].triangleCount != 0) return;
-    const BVHEntry& A = blas[off + blas[off].indexA];
-    const BVHEntry& B = blas[off + blas[off].indexA + 1];
-    if (mesh_cull_boxes(m.worldToLocal, A, B, dm)) dm.cullable = 1;
-    else dm.cull_a_lo = dm.cull_a_hi = dm.cull_b_lo = dm.cull_b_hi = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
-// The child-pair record layout (hg_device.h node_pair): q0 = (A.lo, refA), q1 = (A.hi, refB), q2 = (B.lo, -), q3 = (B.hi, -)
-void put_pair(float4* r, const BVHEntry& A, const BVHEntry& B, uint32_t ra, uint32_t rb) {
-    r[0] = f4(A.boundingCornerA.x, A.boundingCornerA.y, A.boundingCornerA.z, bits(ra));
-    r[1] = f4(A.boundingCornerB.x, A.boundingCornerB.y, A.boundingCornerB.z, bits(rb));
-    r[2] = f4(B.boundingCornerA.x, B.boundingCornerA.y, B.boundingCornerA.z, 0.0f);
-    r[3] = f4(B.boundingCornerB.x, B.boundingCornerB.y, B.boundingCornerB.z, 0.0f);
-}
-
-// fn(begin, end) over [0, n) in contiguous chunks on the persistent host pool (hg_host_pool.h), at most `max_threads`
-// chunks of at least `grain` items
-template <class F>
-void parallel_for(size_t n, size_t grain, int max_threads, F fn) {
-    HgHostPool& pool = HgHostPool::get();
-    const size_t t = std::max<size_t>(1, std::min<size_t>({size_t(max_threads), size_t(pool.threads()),
-                                                           (n + grain - 1) / std::max<size_t>(grain, 1)}));
-    if (t <= 1) {
-        fn(size_t(0), n);
-        return;
-    }
-    const size_t chunk = (n + t - 1) / t;
-    pool.run(t, [&](size_t k) {
-        const size_t b = std::min(n, k * chunk), e = std::min(n, b + chunk);
-        if (b < e) fn(b, e);
-    });
-}
-
-// Byte equality of two buffers, compared in parallel chunks (the scene's triangle array is 63 MB at C3)
-bool same_bytes(const void* a, const void* b, size_t n) {
-    if (n == 0) return true;
-    std::atomic<bool> diff{false};
-    parallel_for(n, size_t(4) << 20, kHostThreads, [&](size_t lo, size_t hi) {
-        constexpr size_t step = size_t(1) << 20;
-        for (size_t i = lo; i < hi && !diff.load(std::memory_order_relaxed); i += step)
-            if (std::memcmp(static_cast<const char*>(a) + i, static_cast<const char*>(b) + i, std::min(step, hi - i)))
-                diff.store(true, std::memory_order_relaxed);
-    });
-    return !diff.load();
-}
-
-void copy_bytes(std::vector<uint8_t>& dst, const void* src, size_t n) {
-    dst.resize(n);
-    if (n == 0) return;
-    parallel_for(n, size_t(4) << 20, kHostThreads, [&](size_t lo, size_t hi) {
-        std::memcpy(dst.data() + lo, static_cast<const char*>(src) + lo, hi - lo);
-    });
 }
 
 int drain_events(hg_ctx* c) {
@@ -635,6 +501,39 @@ int hg_upload_scene(hg_ctx* c, const HalogenSphere* spheres, int32_t n_spheres, 
                                n_nodes);
 }
 
+namespace {
+
+int fail(hg_ctx* c, const HgPackError& err) { return fail(c, err.code, "%s", err.text.c_str()); }
+
+// The bookkeeping of an upload whose device copies are on the stream: the retained host copies the next upload compares
+// against (made while the device copies run), the mesh table a partial re-upload starts from, counters and counts
+int commit_scene(hg_ctx* c, const HgSceneIn& in, HgScenePack& pack, HgUploadDecision d, uint64_t geometry_generation) {
+    const bool partial = d.kind == HG_UPLOAD_PARTIAL;
+    for (int k = 0; k < (partial ? 3 : 5); ++k) copy_bytes(c->scene_copy[k], in.src(k), in.bytes(k));
+    HG_HIP(c, hipStreamSynchronize(c->stream));  // host staging vectors die at return
+    c->dev_meshes.swap(pack.dm);
+    c->scene_uploads++;
+    if (partial) {
+        c->scene_uploads_partial++;
+        c->scene_uploads_vouched += d.vouched ? 1u : 0u;
+    } else {
+        c->stack_depth = pack.stack_depth;
+        c->n_tris = in.n_tris;
+        c->n_nodes = in.n_nodes;
+    }
+    c->geometry_gen = geometry_generation;
+    c->n_spheres = in.n_spheres;
+    c->n_meshes = in.n_meshes;
+    c->n_materials = in.n_materials;
+    c->has_scene = true;
+    return HG_OK;
+}
+
+}  // namespace
+
+// Decision, validation and layout are hg_scene_pack.h's (no HIP; tested on the CPU); here the device and the context.
+// A rejection of the spheres, or of anything in a partial re-upload, leaves the previous scene in place; a rejection in
+// the mesh / BLAS checks of a full rebuild leaves the context without a scene.
 int hg_upload_scene_gen(hg_ctx* c, uint64_t geometry_generation, const HalogenSphere* spheres, int32_t n_spheres,
                         const HalogenMeshData* meshes, int32_t n_meshes, const PackedHalogenMaterial* materials,
                         int32_t n_materials, const HalogenTriangle* tris, int32_t n_tris, const BVHEntry* blas,
@@ -646,246 +545,43 @@ int hg_upload_scene_gen(hg_ctx* c, uint64_t geometry_generation, const HalogenSp
     if ((n_spheres && !spheres) || (n_meshes && !meshes) || (n_materials && !materials) || (n_tris && !tris) ||
         (n_nodes && !blas))
         return fail(c, HG_E_INVALID, "null array with non-zero count");
-    // the traversal addresses nodes / triangles with 32-bit byte offsets (hg_device.h ld_off)
-    if (n_nodes >= (1 << 26) || n_tris >= (1 << 28))
-        return fail(c, HG_E_UNSUPPORTED, "scene too large: %d BLAS entries (max 2^26-1), %d triangles (max 2^28-1)",
-                    n_nodes, n_tris);
-    if (n_materials > 255)
-        return fail(c, HG_E_UNSUPPORTED, "at most 255 materials (medium stack packs material indices in bytes)");
-    // An upload of exactly the arrays already on the device changes nothing: the reference re-uploads every buffer
-    // on each camera move (ClearAccumulation sets ObjectBuffersDirty, RP:262-268, 296-299), and the drop-in keeps that
-    // call pattern.  Compared byte for byte against the retained host copies of the last upload (in parallel; ~3 ms
-    // for C3's 80 MB), it skips the validation, the repack, the copies, the quiesce and the cost-order reset.
-    const void* src[5] = {spheres, meshes, materials, tris, blas};
-    const size_t bytes_in[5] = {size_t(n_spheres) * sizeof(HalogenSphere), size_t(n_meshes) * sizeof(HalogenMeshData),
-                                size_t(n_materials) * sizeof(PackedHalogenMaterial),
-                                size_t(n_tris) * sizeof(HalogenTriangle), size_t(n_nodes) * sizeof(BVHEntry)};
-    bool same[5] = {false, false, false, false, false};
-    // A caller-kept geometry generation equal to the last upload's vouches for the triangles and BVH entries (the C# /
-    // C++ / Python passes bump it when RayTracingManager's mesh registry changes): no compare of those 78 MB (C3).
-    const bool vouched = c->has_scene && geometry_generation != 0 && geometry_generation == c->geometry_gen;
-    if (c->has_scene) {
-        for (int k = 0; k < 5; ++k) same[k] = c->scene_copy[k].size() == bytes_in[k];
-        for (int k = 0; k < 3; ++k)
-            same[k] = same[k] && (!bytes_in[k] || !std::memcmp(c->scene_copy[k].data(), src[k], bytes_in[k]));
-        for (int k = 3; k < 5; ++k)
-            same[k] = same[k] && (vouched || same_bytes(c->scene_copy[k].data(), src[k], bytes_in[k]));
-        if (same[0] && same[1] && same[2] && same[3] && same[4]) {
-            c->scene_uploads_skipped++;
-            c->scene_uploads_vouched += vouched ? 1u : 0u;
-            // (compared equal: the caller's generation now names the device's geometry, so the next upload under it is
-            // vouched for; without this, a first tagged upload of an untagged scene never let the next ones skip the
-            // compare)
-            c->geometry_gen = geometry_generation;
-            return HG_OK;
-        }
-    }
-    c->guides_valid = false;  // the device scene changes: the guide images (hg_update_guides) are another scene's
-    // ---- spheres
-    std::vector<float4> sph(size_t(n_spheres) * 3);
-    for (int i = 0; i < n_spheres; ++i) {
-        const HalogenSphere& s = spheres[i];
-        if (s.materialIndex >= uint32_t(n_materials))
-            return fail(c, HG_E_INVALID, "sphere %d: materialIndex %u out of range", i, s.materialIndex);
-        sph[3 * i] = f4(s.center.x, s.center.y, s.center.z, s.radius);
-        sph[3 * i + 1] = f4(s.boundingCornerA.x, s.boundingCornerA.y, s.boundingCornerA.z, bits(s.materialIndex));
-        sph[3 * i + 2] = f4(s.boundingCornerB.x, s.boundingCornerB.y, s.boundingCornerB.z, 0.0f);
-    }
-    // ---- materials
-    std::vector<float4> mat(size_t(n_materials) * 5);
-    for (int i = 0; i < n_materials; ++i) {
-        const PackedHalogenMaterial& m = materials[i];
-        mat[5 * i] = f4(m.albedo.x, m.albedo.y, m.albedo.z, m.albedo.w);
-        mat[5 * i + 1] = f4(m.specularAlbedo.x, m.specularAlbedo.y, m.specularAlbedo.z, m.metallic);
-        // emissive.rgb * emissive.a (:901) and roughness^2 (:699) are the kernel's own operations done once here
-        mat[5 * i + 2] = f4(m.emissive.x * m.emissive.w, m.emissive.y * m.emissive.w, m.emissive.z * m.emissive.w,
-                            m.roughness);
-        mat[5 * i + 3] = f4(m.rayMedium.absorption.x, m.rayMedium.absorption.y, m.rayMedium.absorption.z,
-                            m.rayMedium.indexOfRefraction);
-        mat[5 * i + 4] = f4(bits(m.rayMedium.priority), bits(m.rayMedium.materialID), m.roughness * m.roughness, 0.0f);
-    }
-    // Partial re-upload: the triangles and the BVH entries are the last upload's and every mesh keeps its buffer
-    // offsets (objects moved, or materials / spheres changed): the node records, leaves, triangles and normals on the
-    // device stay; only the mesh table (world->local matrices, materials, exact-cull boxes), spheres and materials are
-    // rebuilt and copied.  Same device contents as a full upload of these arrays.
-    bool partial = c->has_scene && same[3] && same[4] && size_t(n_meshes) == c->dev_meshes.size() &&
-                   c->scene_copy[1].size() == bytes_in[1];
-    for (int mi = 0; partial && mi < n_meshes; ++mi) {
-        const HalogenMeshData& o = reinterpret_cast<const HalogenMeshData*>(c->scene_copy[1].data())[mi];
-        partial = o.triangleBufferOffset == meshes[mi].triangleBufferOffset &&
-                  o.accelerationBufferOffset == meshes[mi].accelerationBufferOffset;
-    }
-    if (partial) {
-        std::vector<HgDevMesh> dm = c->dev_meshes;
-        for (int mi = 0; mi < n_meshes; ++mi) {
-            const HalogenMeshData& m = meshes[mi];
-            if (m.materialIndex >= uint32_t(n_materials))
-                return fail(c, HG_E_INVALID, "mesh %d: materialIndex %u out of range", mi, m.materialIndex);
-            std::memcpy(dm[mi].w2l, m.worldToLocal.m, sizeof dm[mi].w2l);
-            dm[mi].material = m.materialIndex;
-            set_cull_boxes(m, blas, dm[mi]);
-        }
-        if (int rc = set_device(c)) return rc;
-        if (int rc = quiesce(c)) return rc;  // no trace in flight reads the buffers replaced below
-        c->has_scene = false;
-        int rc;
-        if ((rc = upload(c, c->spheres, sph.data(), sph.size() * sizeof(float4)))) return rc;
-        if ((rc = upload(c, c->materials, mat.data(), mat.size() * sizeof(float4)))) return rc;
-        if ((rc = upload(c, c->meshes, dm.data(), dm.size() * sizeof(HgDevMesh)))) return rc;
-        for (int k = 0; k < 3; ++k) copy_bytes(c->scene_copy[k], src[k], bytes_in[k]);
-        HG_HIP(c, hipStreamSynchronize(c->stream));
-        c->dev_meshes.swap(dm);
-        c->scene_uploads++;
-        c->scene_uploads_partial++;
-        c->scene_uploads_vouched += vouched ? 1u : 0u;
+    const HgSceneIn in{spheres, n_spheres, meshes, n_meshes, materials, n_materials, tris, n_tris, blas, n_nodes};
+    HgPackError err;
+    if (hg_scene_check_limits(in, err)) return fail(c, err);
+    const HgUploadDecision d = hg_upload_decide(c->has_scene, c->scene_copy, c->geometry_gen, c->dev_meshes.size(), in,
+                                                geometry_generation);
+    if (d.kind == HG_UPLOAD_SKIP) {
+        c->scene_uploads_skipped++;
+        c->scene_uploads_vouched += d.vouched ? 1u : 0u;
+        // (compared equal: the caller's generation now names the device's geometry, so the next upload under it is
+        // vouched for; without this, a first tagged upload of an untagged scene never let the next ones skip the
+        // compare)
         c->geometry_gen = geometry_generation;
-        c->n_spheres = n_spheres;
-        c->n_meshes = n_meshes;
-        c->n_materials = n_materials;
-        c->has_scene = true;
         return HG_OK;
     }
+    c->guides_valid = false;  // the device scene changes: the guide images (hg_update_guides) are another scene's
+    const bool partial = d.kind == HG_UPLOAD_PARTIAL;
+    HgScenePack pack;
+    if (hg_pack_spheres_materials(in, pack, err)) return fail(c, err);
+    if (partial && hg_pack_mesh_table(in, c->dev_meshes, pack, err)) return fail(c, err);
     if (int rc = set_device(c)) return rc;
     if (int rc = quiesce(c)) return rc;  // no trace in flight reads the buffers replaced below
     c->has_scene = false;
-    for (auto& v : c->scene_copy) v.clear();
-
-    // ---- triangles (independent per triangle: parallel)
-    const size_t nt = size_t(n_tris);
-    std::vector<float> t9(nt * 9);  // (v0, e1, e2) of tri_load, packed per triangle
-    std::vector<float4> nrm(nt * 3);
-    parallel_for(nt, 32768, kHostThreads, [&](size_t lo, size_t hi) {
-        for (size_t t = lo; t < hi; ++t) {
-            const HalogenTriangle& h = tris[t];
-            const float e1x = h.pointB.x - h.pointA.x, e1y = h.pointB.y - h.pointA.y, e1z = h.pointB.z - h.pointA.z;
-            const float e2x = h.pointC.x - h.pointA.x, e2y = h.pointC.y - h.pointA.y, e2z = h.pointC.z - h.pointA.z;
-            const float v[9] = {h.pointA.x, h.pointA.y, h.pointA.z, e1x, e1y, e1z, e2x, e2y, e2z};
-            std::memcpy(&t9[9 * t], v, sizeof v);
-            nrm[3 * t] = f4(h.normalA.x, h.normalA.y, h.normalA.z, 0.0f);
-            nrm[3 * t + 1] = f4(h.normalB.x - h.normalA.x, h.normalB.y - h.normalA.y, h.normalB.z - h.normalA.z, 0.0f);
-            nrm[3 * t + 2] = f4(h.normalC.x - h.normalA.x, h.normalC.y - h.normalA.y, h.normalC.z - h.normalA.z, 0.0f);
-        }
-    });
-    // ---- BLAS, pass 1: validate every mesh's tree by DFS (ranges, depth, sharing between meshes)
-    std::vector<int64_t> owner(size_t(n_nodes), -1);  // (accOffset << 32 | triOffset) that produced the entry
-    std::vector<HgDevMesh> dm(static_cast<size_t>(n_meshes));
-    uint32_t max_depth = 0;
-    std::vector<std::pair<uint32_t, uint32_t>> dfs;
-    for (int mi = 0; mi < n_meshes; ++mi) {
-        const HalogenMeshData& m = meshes[mi];
-        if (m.materialIndex >= uint32_t(n_materials))
-            return fail(c, HG_E_INVALID, "mesh %d: materialIndex %u out of range", mi, m.materialIndex);
-        const uint32_t off = m.accelerationBufferOffset, toff = m.triangleBufferOffset;
-        if (off >= uint32_t(n_nodes)) return fail(c, HG_E_INVALID, "mesh %d: accelerationBufferOffset out of range", mi);
-        const int64_t key = (int64_t(off) << 32) | int64_t(toff);
-        dfs.assign(1, {off, 0u});
-        while (!dfs.empty()) {
-            auto [g, depth] = dfs.back();
-            dfs.pop_back();
-            if (depth + 2 > kMaxStack)
-                return fail(c, HG_E_UNSUPPORTED, "mesh %d: BLAS deeper than %u levels (or cyclic)", mi, kMaxStack - 2);
-            max_depth = std::max(max_depth, depth);
-            if (owner[g] != -1 && owner[g] != key)
-                return fail(c, HG_E_UNSUPPORTED, "BLAS entry %u shared by meshes with different offsets", g);
-            owner[g] = key;
-            const BVHEntry& e = blas[g];
-            if (e.triangleCount > 0) {
-                if (uint64_t(toff) + e.indexA + e.triangleCount > uint64_t(n_tris))
-                    return fail(c, HG_E_INVALID, "mesh %d: leaf %u references triangles out of range", mi, g);
-            } else {
-                const uint64_t a = uint64_t(off) + e.indexA;
-                if (a + 1 >= uint64_t(n_nodes))
-                    return fail(c, HG_E_INVALID, "mesh %d: node %u has children out of range", mi, g);
-                dfs.push_back({uint32_t(a + 1), depth + 1});
-                dfs.push_back({uint32_t(a), depth + 1});
-            }
-        }
+    if (!partial) {
+        for (auto& v : c->scene_copy) v.clear();
+        if (hg_pack_geometry(in, pack, err)) return fail(c, err);
     }
-    // ---- BLAS, pass 2: device layout.  Inner nodes get a child-pair record (both children's boxes + refs, 64 B),
-    // leaves an entry of the leaf table.  Records are numbered in depth-first pre-order of sibling pairs: the two
-    // children of a node sit in one 128-B line (the far sibling, popped later, is usually still cached) and a
-    // subtree's records are contiguous.  Traversal follows refs only, so visit order and results are unchanged.
-    std::vector<uint32_t> dref(size_t(n_nodes), HG_NONE);  // device ref of each reference BVH entry
-    std::vector<float4> rec;
-    std::vector<uint2> leaf;
-    rec.reserve(size_t(n_nodes) * 4 + 8);
-    auto new_record = [&]() {
-        rec.resize(rec.size() + 4, f4(0, 0, 0, 0));
-        return uint32_t(rec.size() / 4 - 1);
-    };
-    std::vector<uint32_t> expand;
-    for (int mi = 0; mi < n_meshes; ++mi) {
-        const HalogenMeshData& m = meshes[mi];
-        const uint32_t off = m.accelerationBufferOffset, toff = m.triangleBufferOffset;
-        auto ref_for = [&](uint32_t g, bool with_sibling_pad) -> uint32_t {  // assigns a device ref on first use
-            if (dref[g] != HG_NONE) return dref[g];
-            const BVHEntry& e = blas[g];
-            if (e.triangleCount > 0) {
-                const uint64_t first = uint64_t(toff) + e.indexA;
-                if (e.triangleCount <= HG_LEAF_INLINE_MAX && first < HG_LEAF_PAYLOAD) {  // never encodes HG_NONE
-                    dref[g] = HG_LEAF_BIT | (e.triangleCount << HG_LEAF_CNT_SHIFT) | uint32_t(first);
-                } else {
-                    if (leaf.size() > HG_LEAF_PAYLOAD) return HG_NONE;  // reported below
-                    dref[g] = HG_LEAF_BIT | uint32_t(leaf.size());
-                    leaf.push_back(make_uint2(uint32_t(first), e.triangleCount));
-                }
-            } else {
-                if (with_sibling_pad && (rec.size() / 4) % 2 == 1) new_record();  // pair starts on an even record
-                dref[g] = new_record();
-                expand.push_back(g);
-            }
-            return dref[g];
-        };
-        const uint32_t root = ref_for(off, false);
-        if (root == HG_NONE) return fail(c, HG_E_UNSUPPORTED, "too many large BLAS leaves");
-        while (!expand.empty()) {
-            const uint32_t g = expand.back();
-            expand.pop_back();
-            const uint32_t a = off + blas[g].indexA;
-            const bool both_new = dref[a] == HG_NONE && dref[a + 1] == HG_NONE && blas[a].triangleCount == 0 &&
-                                  blas[a + 1].triangleCount == 0;
-            const size_t mark = expand.size();
-            const uint32_t ra = ref_for(a, both_new);
-            const uint32_t rb = ref_for(a + 1, false);
-            if (ra == HG_NONE || rb == HG_NONE) return fail(c, HG_E_UNSUPPORTED, "too many large BLAS leaves");
-            if (expand.size() == mark + 2) std::swap(expand[mark], expand[mark + 1]);  // expand child A first
-            const BVHEntry& A = blas[a];
-            const BVHEntry& B = blas[a + 1];
-            put_pair(&rec[4 * size_t(dref[g])], A, B, ra, rb);
-        }
-        std::memcpy(dm[mi].w2l, m.worldToLocal.m, sizeof dm[mi].w2l);
-        dm[mi].root_ref = root;
-        dm[mi].tri_offset = toff;
-        dm[mi].material = m.materialIndex;
-        set_cull_boxes(m, blas, dm[mi]);
-    }
-    if (rec.size() / 4 >= (size_t(1) << 26))
-        return fail(c, HG_E_UNSUPPORTED, "BLAS too large: %zu device node records", rec.size() / 4);
-    if (rec.empty()) new_record();
-    if (leaf.empty()) leaf.push_back(make_uint2(0, 0));
-    c->stack_depth = std::max<uint32_t>(2u, (max_depth + 2 + 1) & ~1u);
-
     int rc;
-    if ((rc = upload(c, c->spheres, sph.data(), sph.size() * sizeof(float4)))) return rc;
-    if ((rc = upload(c, c->materials, mat.data(), mat.size() * sizeof(float4)))) return rc;
-    if ((rc = upload(c, c->meshes, dm.data(), dm.size() * sizeof(HgDevMesh)))) return rc;
-    if ((rc = upload(c, c->nodes, rec.data(), rec.size() * sizeof(float4)))) return rc;
-    if ((rc = upload(c, c->leaves, leaf.data(), leaf.size() * sizeof(uint2)))) return rc;
-    if ((rc = upload(c, c->tris, t9.data(), t9.size() * sizeof(float)))) return rc;
-    if ((rc = upload(c, c->normals, nrm.data(), nrm.size() * sizeof(float4)))) return rc;
-    // the retained copies the next upload compares against (while the device copies run)
-    for (int k = 0; k < 5; ++k) copy_bytes(c->scene_copy[k], src[k], bytes_in[k]);
-    c->dev_meshes = dm;
-    HG_HIP(c, hipStreamSynchronize(c->stream));  // host staging vectors die at return
-    c->geometry_gen = geometry_generation;
-    c->scene_uploads++;
-    c->n_spheres = n_spheres;
-    c->n_meshes = n_meshes;
-    c->n_materials = n_materials;
-    c->n_tris = n_tris;
-    c->n_nodes = n_nodes;
-    c->has_scene = true;
-    return HG_OK;
+    if ((rc = upload(c, c->spheres, pack.sph.data(), pack.sph.size() * sizeof(float4)))) return rc;
+    if ((rc = upload(c, c->materials, pack.mat.data(), pack.mat.size() * sizeof(float4)))) return rc;
+    if ((rc = upload(c, c->meshes, pack.dm.data(), pack.dm.size() * sizeof(HgDevMesh)))) return rc;
+    if (!partial) {
+        if ((rc = upload(c, c->nodes, pack.rec.data(), pack.rec.size() * sizeof(float4)))) return rc;
+        if ((rc = upload(c, c->leaves, pack.leaf.data(), pack.leaf.size() * sizeof(uint2)))) return rc;
+        if ((rc = upload(c, c->tris, pack.t9.data(), pack.t9.size() * sizeof(float)))) return rc;
+        if ((rc = upload(c, c->normals, pack.nrm.data(), pack.nrm.size() * sizeof(float4)))) return rc;
+    }
+    return commit_scene(c, in, pack, d, geometry_generation);
 }
 
 int hg_upload_cubemap(hg_ctx* c, int32_t face_size, int32_t n_mips, const float* texels, size_t n_floats) {

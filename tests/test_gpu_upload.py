@@ -12,7 +12,7 @@ import pytest
 import cases
 from halogen import abi
 from halogen.scene import PackedScene
-from test_gpu_parity import assert_bitwise, gpu_render
+from test_gpu_parity import GOLD, assert_bitwise, gpu_render
 
 
 def _copy(packed):
@@ -124,7 +124,7 @@ def test_gpu_partial_reupload_sphere_count_and_cull_flip(gpu, name):
     W, H = int(params.screenParameters.x), int(params.screenParameters.y)
     fewer = _with_spheres(packed, len(packed.spheres) - 1)
     singular = _copy(packed)
-    for i in (0, 1, 2, 4, 5, 6, 8, 9, 10):  # the linear part scaled by 1e-11: |det| ~ 1e-33 (hg_runtime.hip invert4)
+    for i in (0, 1, 2, 4, 5, 6, 8, 9, 10):  # the linear part scaled by 1e-11: |det| ~ 1e-33 (hg_scene_pack.h invert4)
         singular.meshes[0].worldToLocal.m[i] = np.float32(singular.meshes[0].worldToLocal.m[i] * 1e-11)
     for variant, what in ((fewer, "one sphere fewer"), (singular, "a mesh no longer cullable"),
                           (packed, "back to the first scene")):
@@ -195,3 +195,45 @@ def test_gpu_upload_generation_vouches_for_geometry(gpu):
         ctx.upload_scene(changed, generation=8)  # a new generation: compared again (equal: skipped, not vouched)
         c3 = ctx.counters()
         assert c3["scene_uploads_skipped"] == 3 and c3["scene_uploads_vouched"] == 2, c3
+
+
+@pytest.mark.gpu
+def test_gpu_rejected_upload_leaves_its_documented_state(gpu):
+    """The two states a rejected hg_upload_scene leaves behind.  A rejection before the device scene is touched (here
+    a sphere's materialIndex) keeps the previous scene: the accumulation continues bit-identically.  A rejection in the
+    mesh / BLAS checks of a full rebuild (here a mesh's accelerationBufferOffset) leaves the context without a scene:
+    hg_render says so until a good upload.  Both bad uploads are refused on the host; nothing of them reaches the
+    device."""
+    packed, params, cube, frames, acc = cases.setup("c1_64")
+    W, H = int(params.screenParameters.x), int(params.screenParameters.y)
+    gold = np.load(GOLD / "c1_64.npz")["image"]
+    bad_sphere = _copy(packed)
+    bad_sphere.spheres[0].materialIndex = len(packed.materials)
+    bad_mesh = _copy(packed)
+    bad_mesh.meshes[1].accelerationBufferOffset = len(packed.blas)
+    with abi.Context(0) as ctx:
+        ctx.upload_scene(packed)
+        ctx.resize(W, H)
+        ctx.set_params(params)
+        ctx.render(2, True)
+        with pytest.raises(abi.HalogenError) as e:
+            ctx.upload_scene(bad_sphere)
+        assert e.value.rc == abi.HG_E_INVALID
+        assert str(e.value).endswith(f"sphere 0: materialIndex {len(packed.materials)} out of range"), str(e.value)
+        ctx.render(frames - 2, True)  # the previous scene is still there
+        assert_bitwise(ctx.readback(W, H), gold, "c1_64 continued after a rejected sphere")
+        with pytest.raises(abi.HalogenError) as e:
+            ctx.upload_scene(bad_mesh)
+        assert e.value.rc == abi.HG_E_INVALID
+        assert str(e.value).endswith("mesh 1: accelerationBufferOffset out of range"), str(e.value)
+        with pytest.raises(abi.HalogenError) as e:
+            ctx.render(1, True)
+        assert e.value.rc == abi.HG_E_NOSCENE and "hg_upload_scene not called" in str(e.value), str(e.value)
+        ctx.upload_scene(packed)
+        ctx.clear_accumulation()
+        ctx.set_params(params)
+        ctx.render(frames, True)
+        img = ctx.readback(W, H)
+        cnt = ctx.counters()
+    assert cnt["scene_uploads"] == 2 and cnt["scene_uploads_skipped"] == 0, cnt
+    assert_bitwise(img, gold, "c1_64 after the context lost and regained its scene")

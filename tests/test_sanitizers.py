@@ -23,6 +23,7 @@ ROOT = Path(__file__).resolve().parents[1]
 ASAN = ROOT / "oracle" / "build" / "hg_oracle_asan"
 TSAN = ROOT / "halogen-pathtracer_amd" / "build" / "tsan_blas"
 ASAN_SAH = ROOT / "halogen-pathtracer_amd" / "build" / "asan_sah"
+ASAN_SCENE_PACK = ROOT / "halogen-pathtracer_amd" / "build" / "asan_scene_pack"
 ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
            UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1", TSAN_OPTIONS="halt_on_error=1:exitcode=66")
 
@@ -108,3 +109,15 @@ def test_sah_builder_under_asan_ubsan():
     out = run([ASAN_SAH, 20000, 7])
     assert out.count("every triangle in one leaf") == 12, out
     assert out.count("non-finite vertex rejected") == 2, out
+
+
+def test_scene_pack_under_asan_ubsan():
+    """hg_upload_scene's validation and device layout (csrc/hg_scene_pack.h) under AddressSanitizer + UBSan, as a
+    stand-alone program (host/asan_scene_pack.cpp): the smallest trees of each shape, every rejection with its code and
+    text, 300 seeded random scenes checked by the host walk (host/scene_pack_check.h), and 8 single-field corruptions
+    of each (a mesh offset, an indexA or a triangleCount replaced by a random value), every one of them rejected or
+    packed into a scene whose refs, table indices and triangle ranges the walk finds in bounds."""
+    subprocess.run(["make", "-s", "-C", str(ROOT / "halogen-pathtracer_amd"), "asan_scene_pack"], check=True)
+    out = run([ASAN_SCENE_PACK, 300, 11])
+    assert "hand-made trees and rejections done" in out and out.rstrip().endswith("scene pack ok"), out
+    assert "FAILED" not in out, out
