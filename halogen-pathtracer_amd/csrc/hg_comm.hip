@@ -43,7 +43,7 @@
 #include <vector>
 
 #include "halogen_abi.h"
-#include "hg_ctx.h"
+#include "hg_rt.h"
 #include "hg_layout.h"
 #include "hg_tiling.h"
 

@@ -1,5 +1,5 @@
-// hg_ctx.h — the context object behind the C-ABI's opaque hg_ctx (private to libhalogen_hip.so; shared by
-// hg_runtime.hip and hg_comm.hip).
+// hg_ctx.h — the context object behind the C-ABI's opaque hg_ctx (private to libhalogen_hip.so; the functions over it
+// that its translation units share are declared in hg_rt.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +10,7 @@
 
 #include "halogen_abi.h"
 #include "hg_layout.h"
+#include "hg_slot_ring.h"
 
 struct DevBuf {  // a device allocation owned by a context
     void* p = nullptr;
@@ -89,8 +90,7 @@ struct hg_ctx {
         DevBuf ctl;         // heads, mirror, ticket (HG_SV_CTL_BYTES), zeroed before each launch
         DevBuf done;        // per ring slot a completion count on its own 128-B line, zeroed before each launch
         DevBuf ring;        // colour ring: ring_n frames of n_local_tiles * 64 float4
-        DevBuf spill, tile_cost, tile_order, order_scratch;
-        bool tile_cost_valid = false;
+        DevBuf spill;
         unsigned long long* host = nullptr;  // pinned, coherent: the host words HG_SV_HOST_* (hg_layout.h)
         uint32_t ring_n = 0, posted = 0, cap = 0;
         uint32_t committed = 0;  // frames the host asked for (gate + blend queued); posted - committed were posted ahead
@@ -156,21 +156,23 @@ struct hg_ctx {
     int32_t coalesce = HG_COALESCE;
     int32_t pending_frames = 0, pending_acc = 0;
 
-    // Display readback (hg_readback, hg_readback_begin[_format] / _end[_data]): the accumulator untiled on the device
-    // into `image` (row-major, in the display format), then copied into the next of rb_depth pinned host images (a ring)
-    DevBuf image;
-    void* image_host[HG_READBACK_MAX] = {};
-    size_t image_host_cap[HG_READBACK_MAX] = {};    // allocated bytes
-    size_t image_host_bytes[HG_READBACK_MAX] = {};  // bytes of the readback it holds
-    int32_t image_host_format[HG_READBACK_MAX] = {};
-    bool image_host_mapped[HG_READBACK_MAX] = {};  // allocated mapped + fine-grained (HG_OPT_READBACK_STREAM 2)
-    hipEvent_t image_copied[HG_READBACK_MAX] = {};
-    int rb_depth = 2;                 // HG_OPT_READBACK_DEPTH: readbacks that may be outstanding
-    int rb_side = HG_READBACK_SIDE;   // HG_OPT_READBACK_STREAM: copies on rb_stream from per-slot device images
-    hipStream_t rb_stream = nullptr;
-    DevBuf rb_image[HG_READBACK_MAX];
-    hipEvent_t rb_untiled[HG_READBACK_MAX] = {};
-    int rb_next = 0, rb_pending = 0;  // host image the next begin fills; begun readbacks not yet ended (<= rb_depth)
+    // Display readback (hg_display.hip: hg_readback, hg_readback_begin[_format] / _end[_data]): the accumulator untiled on
+    // the device into a row-major image in the display format, which ends up in the next of rb.depth slots (a ring)
+    struct DisplaySlot {
+        void* host = nullptr;  // the pinned host image the caller reads
+        size_t cap = 0;        // its allocated bytes
+        size_t bytes = 0;      // bytes of the readback it holds
+        int32_t format = 0;
+        bool mapped = false;   // allocated mapped + fine-grained (HG_OPT_READBACK_STREAM 2 untiles straight into it)
+        hipEvent_t copied = nullptr;   // after the readback's last write to `host`
+        DevBuf image;                  // HG_OPT_READBACK_STREAM 1: the slot's own device image, copied on rb_stream
+        hipEvent_t untiled = nullptr;  // ... after the untile into it (the copy on rb_stream waits for it)
+    };
+    DevBuf image;  // HG_OPT_READBACK_STREAM 0 and hg_readback: the one device image, copied on `stream`
+    DisplaySlot slots[HG_READBACK_MAX];
+    HgSlotRing rb;                    // HG_OPT_READBACK_DEPTH; the slot the next begin fills, begun readbacks not yet ended
+    int rb_side = HG_READBACK_SIDE;   // HG_OPT_READBACK_STREAM
+    hipStream_t rb_stream = nullptr;  // created at the first begin that copies on it
 
     // Denoised display (hg_update_guides, hg_readback_begin_denoised; kernels in hg_denoise.hip): the guide images
     // (row-major W x H float4: normal + t, albedo + kind) and the filter's two colour images, all allocated by
@@ -179,12 +181,3 @@ struct hg_ctx {
     DevBuf guide0, guide1, denoise_work[2];
     bool guides_valid = false;
 };
-
-// Launch the held frames of a context, if any (hg_runtime.hip; every entry point but hg_render calls it first)
-int hg_ctx_flush(hg_ctx* c);
-// The context's accumulation is invalid (a render server frame was lost; reads the gates' report first)
-bool hg_ctx_lost(hg_ctx* c);
-// Enqueue a display readback (hg_readback_begin_format) from the accumulator (rows == nullptr) or from a row-major
-// float4 image of the target's size on the context's device; and the copy event of the oldest outstanding one
-int hg_ctx_display_begin(hg_ctx* c, const void* rows, int32_t format);
-hipEvent_t hg_ctx_display_oldest(const hg_ctx* c);

@@ -3,13 +3,16 @@
 // arithmetic csrc/hg_atrous.h defines for this file and for the host twin hg_denoise_host alike.  Not in the reference.
 //
 // A translation unit of its own: the kernels of hg_mega.hip and hg_query.hip compile to what they compile to without it.
+// The kernels and their launchers first, then the entry points of the C-ABI.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 
 #include "halogen_abi.h"
 #include "hg_atrous.h"
 #include "hg_device.h"
+#include "hg_rt.h"
 #include "hg_tiling.h"
 
 using namespace hgd;
@@ -84,7 +87,7 @@ hipError_t hg_launch_guides(const HgKernelParams& kp, uint32_t frame, void* guid
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The filter.  Every kernel here is a one-wave workgroup with no LDS, as the display untile is (hg_runtime.hip
+// The filter.  Every kernel here is a one-wave workgroup with no LDS, as the display untile is (hg_display.hip
 // launch_untile): a per-frame display runs them beside the render server's persistent trace waves, which hold most
 // wave slots, and a larger workgroup would wait for a CU to drain.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -207,3 +210,78 @@ hipError_t hg_launch_denoise(const void* acc, const void* guide0, const void* gu
     *result = work[at];
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The entry points
+// ---------------------------------------------------------------------------------------------------------------------
+using namespace hgrt;
+
+extern "C" {
+
+int hg_update_guides(hg_ctx* c, const hg_params* p, int32_t frame_count) {
+    if (!c) return HG_E_INVALID;
+    if (!p) return fail(c, HG_E_INVALID, "null params");
+    if (!c->has_scene) return fail(c, HG_E_NOSCENE, "hg_upload_scene not called");
+    if (c->W <= 0) return fail(c, HG_E_NOTARGET, "hg_resize not called");
+    if (!(p->screenParameters.x == float(c->W) && p->screenParameters.y == float(c->H)))
+        return fail(c, HG_E_INVALID, "screenParameters (%g,%g) are not the target's size %dx%d", p->screenParameters.x,
+                    p->screenParameters.y, c->W, c->H);
+    if (int rc = query_begin(c)) return rc;
+    // the context is idle: the four images may move
+    c->guides_valid = false;
+    const size_t pixels = size_t(c->W) * size_t(c->H);
+    for (DevBuf* b : {&c->guide0, &c->guide1, &c->denoise_work[0], &c->denoise_work[1]})
+        if (int rc = ensure(c, *b, pixels * sizeof(float4))) return rc;
+    // the closest-hit query's parameter block (the whole uploaded scene, far = +inf) with the caller's camera
+    HgKernelParams kp;
+    if (int rc = query_params(c, hg_guides_threads(uint32_t(std::min<size_t>(pixels, size_t(kQueryChunk)))), kp)) return rc;
+    const float far_ = kp.far_;
+    set_camera(kp, *p);
+    kp.far_ = far_;
+    for (size_t at = 0; at < pixels; at += size_t(kQueryChunk)) {  // in stream order: the launches share the spill buffer
+        const uint32_t m = uint32_t(std::min(pixels - at, size_t(kQueryChunk)));
+        HG_HIP(c, hg_launch_guides(kp, uint32_t(frame_count), c->guide0.p, c->guide1.p, uint32_t(at), m, c->stream));
+    }
+    HG_HIP(c, hipStreamSynchronize(c->stream));
+    c->guides_valid = true;
+    return HG_OK;
+}
+
+int hg_readback_guides(hg_ctx* c, float* guide0, float* guide1, size_t n_floats_each) {
+    if (!c) return HG_E_INVALID;
+    if (c->W <= 0) return fail(c, HG_E_NOTARGET, "hg_resize not called");
+    if (!c->guides_valid) return fail(c, HG_E_INVALID, "no guide images for this scene and target: call hg_update_guides");
+    const size_t bytes = size_t(c->W) * size_t(c->H) * sizeof(float4);
+    if (n_floats_each * sizeof(float) < bytes) return fail(c, HG_E_INVALID, "guide buffer too small");
+    if (int rc = set_device(c)) return rc;
+    if (guide0) HG_HIP(c, hipMemcpyAsync(guide0, c->guide0.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (guide1) HG_HIP(c, hipMemcpyAsync(guide1, c->guide1.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HG_HIP(c, hipStreamSynchronize(c->stream));
+    return HG_OK;
+}
+
+int hg_readback_begin_denoised(hg_ctx* c, int32_t format, const hg_denoise_params* p) {
+    if (!c) return HG_E_INVALID;
+    if (!p) return fail(c, HG_E_INVALID, "null denoise params");
+    if (!hg_atrous_params_ok(*p))
+        return fail(c, HG_E_INVALID,
+                    "bad denoise params: iterations %d (1..%d), sigmas %g %g %g (off, or in [1e-4, 1e4]), demodulate %d, "
+                    "flags %u", p->iterations, HG_ATROUS_MAX_ITERATIONS, p->sigma_color, p->sigma_normal, p->sigma_depth,
+                    p->demodulate, p->flags);
+    if (int rc = hg_ctx_flush(c)) return rc;
+    if (int rc = display_check(c, format)) return rc;  // (a full ring refuses before the filter is launched)
+    if (c->n_ranks > 1)
+        return fail(c, HG_E_UNSUPPORTED, "denoised display of a tiled context (rank %d of %d): a rank's share has no "
+                    "neighbours", c->rank, c->n_ranks);
+    if (int64_t(c->W) * c->H > HG_ATROUS_MAX_PIXELS)
+        return fail(c, HG_E_UNSUPPORTED, "denoised display of more than 2^28 pixels (%dx%d)", c->W, c->H);
+    if (!c->guides_valid) return fail(c, HG_E_INVALID, "no guide images for this scene and target: call hg_update_guides");
+    if (int rc = set_device(c)) return rc;
+    // on the context stream, after every frame rendered so far (the server keeps tracing: nothing here waits)
+    void* const work[2] = {c->denoise_work[0].p, c->denoise_work[1].p};
+    const void* denoised = nullptr;
+    HG_HIP(c, hg_launch_denoise(c->acc.p, c->guide0.p, c->guide1.p, work, c->W, c->H, c->tiles_x, *p, c->stream, &denoised));
+    return hg_ctx_display_begin(c, denoised, format);
+}
+
+}  // extern "C"

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "hg_device.h"
+#include "hg_launch.h"
 
 using namespace hgd;
 
@@ -1026,7 +1027,7 @@ __device__ uint32_t sv_view(const HgKernelParams& kp) {
     const unsigned long long m = sv_sload(sv_word64(kp, HG_SV_MIRROR_WORD + 32u * (blockIdx.x % HG_SV_MIRRORS)));
     const uint32_t u = sv_units(m);
     // a post word with the stop flag is final: its count may be below the frames posted ahead of the host's calls
-    // (hg_runtime.hip server_speculate), which are abandoned (the units already pulled are traced)
+    // (hg_render.hip server_speculate), which are abandoned (the units already pulled are traced)
     if (u > v || ((m & HG_SV_STOP) && u != v)) {
         v = u;
         lds_put(hg_sv.view, v);
@@ -1178,7 +1179,7 @@ __device__ bool sv_refill(const HgKernelParams& kp) {
 // consistent: the store is visible to the host before the load is performed), and publishes the post word it read with
 // the stop flag, to the host (the close word, HG_SV_CLOSED) and to every mirror (atomic max: the stop flag outranks
 // every post word without it, so a poller that read a later post word cannot raise a view past it).  Every wave then
-// drains the frames of that view and leaves.  The host's side is hg_runtime.hip server_post.
+// drains the frames of that view and leaves.  The host's side is hg_render.hip server_post_frame.
 __device__ void sv_close(const HgKernelParams& kp) {
     uint32_t* const word = kp.queue + HG_SV_CLOSE_WORD;
     if (ld_agent(word) != 0u || atomicCAS(word, 0u, 1u) != 0u) return;  // another wave closes it
@@ -1595,7 +1596,7 @@ hipError_t hg_launch_mega_stream(const HgKernelParams& kp_in, int block, bool co
     return hipGetLastError();
 }
 
-// The render server's per-frame work on the context stream (hg_runtime.hip server_post): the gate waits until the
+// The render server's per-frame work on the context stream (hg_render.hip server_commit): the gate waits until the
 // frame's ring-slot count reaches `target` (one wave; agent-scope polls with a sleep).  It gives up when every wave of
 // the server has left with the count still short (the frame can no longer complete), or after `timeout_ticks`: then
 // the frame is lost, and the gate raises the context's lost word (device memory: every later blend into the
@@ -1651,7 +1652,7 @@ hipError_t hg_launch_server_frame(float4* acc, const float4* colors, uint32_t n_
     return hipGetLastError();
 }
 
-// Launcher used by the runtime (hg_runtime.hip)
+// Launcher used by the runtime (hg_render.hip)
 hipError_t hg_launch_mega(const HgKernelParams& kp, int block, bool counters, hipStream_t stream) {
     const int tiles_per_block = block / 64;
     const int grid = (kp.n_local_tiles + tiles_per_block - 1) / tiles_per_block;

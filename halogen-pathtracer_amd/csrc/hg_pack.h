@@ -1,5 +1,5 @@
 // hg_pack.h — the display formats of hg_readback_begin_format (include/halogen_abi.h), one definition for the device
-// untile kernel (hg_runtime.hip) and the host packer hg_pack_display.
+// untile kernel (hg_display.hip) and the host packer hg_pack_display.
 //
 // The reference blits its accumulation target into the URP camera colour target (HalogenRenderPass.cs:345), which
 // Assets/Settings/URP-HighFidelity.asset:26-27 configures as an HDR target of m_HDRColorBufferPrecision 0: the 32-bit

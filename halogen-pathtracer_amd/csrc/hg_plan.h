@@ -1,5 +1,5 @@
 // hg_plan.h — the launch plan of hg_render: every decision about the shape of a launch, as plain functions of plain
-// integers.  No HIP, no hg_ctx, no streams, no allocation: hg_runtime.hip fills an HgPlanIn from the context, asks
+// integers.  No HIP, no hg_ctx, no streams, no allocation: hg_render.hip fills an HgPlanIn from the context, asks
 // here, and issues the HIP calls; tests/test_launch_plan.py compiles this header with g++ and checks the arithmetic
 // (every plan renders the same image, so a wrong plan shows only as a slower one: no rendering test can see it).
 #pragma once

@@ -3,6 +3,8 @@
 
 #include <cstdint>
 
+#include "hg_launch.h"
+
 // ---------------------------------------------------------------------------------------------------------
 // self-test: the fast reciprocal path against IEEE division for all 2^32 inputs of its range
 // ---------------------------------------------------------------------------------------------------------

@@ -90,7 +90,7 @@
 // stream of the process, and two streams on one queue run their launches one after the other (a third plain trace
 // stream cost 1-frame launches 16 %: 1,663 vs 1,970).  A stream created with a CU mask gets a hardware queue of its
 // own: the first HG_TRACE_LANES_BIG trace streams are plain and non-blocking, the others (and the render server's and
-// the side copy stream) carry an all-CU mask (create_lane_stream, hg_runtime.hip).
+// the side copy stream) carry an all-CU mask (create_masked_stream, hg_runtime.hip).
 #ifndef HG_QUEUE_WAVES_DIV
 #define HG_QUEUE_WAVES_DIV 8  // queue launches beside >= 2 other traces in flight: at most this many times fewer persistent
 #endif                        // waves than resident slots (hg_render; C3 1-frame launches, 8 streams: 1 2,265 -> 6 2,745;
@@ -158,15 +158,7 @@
 #define HG_SV_POLL_EVERY 4u  // an idle wave reads the host word (if its XCD's ticket is free) every this many spins
 #endif
 #ifndef HG_SV_WAVES
-#define HG_SV_WAVES 5  // the render server's persistent waves per SIMD (hg_runtime.hip server_start)
-#endif
-#ifndef HG_SV_COST_ORDER
-// The render server's units in the cost order of its last lifetime's frames (1) or in raster order with no cost records
-// (0).  The cost order puts a launch's longest tiles first so that its end waits less on them; the server's frames
-// overlap, so there is no such end, and raster order keeps a claim's consecutive tiles together.  C3, server forced,
-// one box, two rounds (tools/sweeps/sweep_r06_server_order.txt): strict 3,155 / 3,159 -> 3,168 / 3,164, display at once (R11G11B10F)
-// 2,662 / 2,669 -> 2,752 / 2,726 Mpaths/s.
-#define HG_SV_COST_ORDER 0
+#define HG_SV_WAVES 5  // the render server's persistent waves per SIMD (hg_render.hip server_start)
 #endif
 #ifndef HG_SV_TILE_RUN
 // The render server's XCD heads take runs of this many consecutive tiles (hg_mega.hip sv_pull): head h (the XCD whose

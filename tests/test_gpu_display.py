@@ -66,6 +66,38 @@ def test_gpu_display_format_equals_host_packing(gpu, fmt, side):
 
 
 @pytest.mark.gpu
+def test_gpu_display_slot_image_across_modes(gpu):
+    """A slot's pinned host image across HG_OPT_READBACK_STREAM 2 -> 1 -> 0 -> 2 with a growing display format: allocated
+    mapped (zero copy), reused mapped by the side-stream copy, grown as a plain image by the context-stream copy, and
+    replaced by a mapped one; three begins per step pass through both slots of a depth-2 ring, two of them outstanding
+    at once.  Every image equals the host packing of the RGBA32F readback, and the accumulation target is untouched."""
+    packed, params, cube, frames, acc = cases.setup("c1_64")
+    W, H = int(params.screenParameters.x), int(params.screenParameters.y)
+    with abi.Context(0) as ctx:
+        ctx.upload_scene(packed)
+        ctx.resize(W, H)
+        ctx.set_params(params)
+        ctx.set_option(abi.HG_OPT_READBACK_DEPTH, 2)
+        ctx.render(1, True)
+        want = ctx.readback(W, H)
+        steps = [(2, abi.HG_DISPLAY_R11G11B10F), (1, abi.HG_DISPLAY_RGBA16F), (0, abi.HG_DISPLAY_RGBA32F),
+                 (2, abi.HG_DISPLAY_R11G11B10F)]
+        for step, (side, fmt) in enumerate(steps):
+            ctx.set_option(abi.HG_OPT_READBACK_STREAM, side)
+            host = abi.pack_display(want, fmt)
+            ctx.readback_begin(fmt)  # slot 0
+            ctx.readback_begin(fmt)  # slot 1
+            got = [ctx.readback_end(W, H), ctx.readback_end(W, H)]
+            ctx.readback_begin(fmt)  # slot 0 again
+            got.append(ctx.readback_end(W, H))
+            for k, img in enumerate(got):
+                assert img.shape == host.shape and img.dtype == host.dtype, (step, k)
+                bad = int((_bits(img) != _bits(host)).sum())
+                assert bad == 0, f"step {step} (stream {side}, format {fmt}), readback {k}: {bad} values differ"
+        assert_bitwise(ctx.readback(W, H), want, "accumulation target after the display readbacks")
+
+
+@pytest.mark.gpu
 def test_gpu_display_format_tiling(gpu):
     """With a tiling, the other ranks' pixels pack as 0 in every format."""
     packed, params, cube, frames, acc = cases.setup("c1_64")

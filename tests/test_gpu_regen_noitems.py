@@ -1,6 +1,6 @@
 """Pipelined launches whose last chunk is a single frame.
 
-A regenerating launch on the trace pipeline (hg_plan.h hg_plan_call, launched by hg_runtime.hip launch_pipelined) is chunked at HG_REGEN_MAX_CHUNK frames, or at
+A regenerating launch on the trace pipeline (hg_plan.h hg_plan_call, launched by hg_render.hip launch_pipelined) is chunked at HG_REGEN_MAX_CHUNK frames, or at
 fewer when the per-frame colour buffer would pass its 4 GiB cap (2048 x 2048: 64 MiB per frame -> 64-frame chunks).  With
 a frame split of 3, a 65-frame launch is one 64-frame chunk split 3 ways and one 1-frame chunk, whose own split is 1.
 Every chunk of a pipelined launch is blended in frame order afterwards, so every chunk must store its colours, the

@@ -2,9 +2,10 @@
 per-tile waves, the trace stream class, spill bytes, the hold window and the render server's sizing.  Every plan renders
 the same image, so a wrong plan only runs slower and no rendering test can see it: here the header is compiled with g++
 (no HIP, no GPU) and checked against the values the code comments state for a 256-CU GPU, against a Python restatement
-of the arithmetic as hg_runtime.hip had it before the plan was split out, and the server's unit -> frame magic divide
-against integer division.  Also the inverse tile mapping of csrc/hg_tiling.h and the event-pair scope guard of
-csrc/hg_pair_guard.h, through the same driver."""
+of the arithmetic as hg_runtime.hip had it before the plan was split out (the launches are now hg_render.hip's), and
+the server's unit -> frame magic divide against integer division.  Also the inverse tile mapping of csrc/hg_tiling.h, the event-pair scope guard of
+csrc/hg_pair_guard.h and the display slot ring of csrc/hg_slot_ring.h, through the same driver."""
+import collections
 import random
 import subprocess
 from pathlib import Path
@@ -19,6 +20,7 @@ DRIVER = r'''
 #include "hg_plan.h"
 #include "hg_tiling.h"
 #include "hg_pair_guard.h"
+#include "hg_slot_ring.h"
 #include <cstdio>
 #include <cstring>
 #include <utility>
@@ -136,10 +138,30 @@ static void guard() {
     }
 }
 
+// the display slot ring under a scripted sequence: "b" begin, "e" end, "r" reset, "d <depth>" set_depth; each answers
+// with "<slot> <full> <pending> <oldest>" (-1 for no slot: begin on a full ring and end on an empty one are not called,
+// as the runtime checks first)
+static void ring() {
+    unsigned n;
+    if (std::scanf("%u", &n) != 1) return;
+    HgSlotRing r;
+    for (unsigned i = 0; i < n; ++i) {
+        char op[4];
+        int d = 0, slot = -1;
+        if (std::scanf("%3s", op) != 1) return;
+        if (op[0] == 'b' && !r.full()) slot = r.begin();
+        if (op[0] == 'e' && r.pending > 0) slot = r.end();
+        if (op[0] == 'r') r.reset();
+        if (op[0] == 'd' && std::scanf("%d", &d) == 1) r.set_depth(d);
+        std::printf("%d %d %d %d\n", slot, int(r.full()), r.pending, r.pending > 0 ? r.oldest() : -1);
+    }
+}
+
 int main() {
     char what[16];
     while (std::scanf("%15s", what) == 1) {
         if (!std::strcmp(what, "plan")) plan();
+        else if (!std::strcmp(what, "ring")) ring();
         else if (!std::strcmp(what, "divide")) divide();
         else if (!std::strcmp(what, "tiling")) tiling();
         else if (!std::strcmp(what, "guard")) guard();
@@ -214,7 +236,7 @@ def slots_of(n_cu, waves):
 
 
 def restate_chunk(c, P, frames, prefix):
-    """hg_runtime.hip render_now's per-chunk decisions, as they stood in the chunk loop of its pipelined branch."""
+    """render_now's per-chunk decisions (now hg_render.hip), as they stood in the chunk loop of its pipelined branch."""
     tiles, slots = c["tiles"], slots_of(c["n_cu"], STREAM_WAVES)
     frame_split = min(P["split"], frames)
     fill = c["queue_fill"] > 0 and tiles * frames < c["queue_fill"] * slots * 64
@@ -229,7 +251,7 @@ def restate_chunk(c, P, frames, prefix):
 
 def restate(c, items):
     """The decisions of render_now, hold_window and server_start restated from hg_runtime.hip as it was before
-    hg_plan.h, in the order of its lines (tiles >= 1)."""
+    hg_plan.h (the three now live in hg_render.hip), in the order of its lines (tiles >= 1)."""
     tiles, n_frames, n_cu = c["tiles"], c["n_frames"], c["n_cu"]
     # hold_window
     w = c["coalesce"]
@@ -438,3 +460,46 @@ def test_event_pair_guard(driver):
         "0 free 7,8 pending",     # dismissed by hand, not returned again at scope end
         "0 free 7,8 pending 9,10",  # a second pair: the first goes back, the second is handed on
     ]
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3, 16])  # 16: HG_READBACK_MAX
+def test_slot_ring(driver, depth):
+    """The display readback ring (hg_ctx::rb) against a deque of the outstanding slots, over a seeded random sequence of
+    begin / end / reset / set_depth (the depth changes only with nothing outstanding, as HG_OPT_READBACK_DEPTH demands):
+    full() exactly when `depth` slots are outstanding, begin() never hands out an outstanding slot, end() returns the
+    slots in begin order, and set_depth and reset restart at slot 0."""
+    exe, _ = driver
+    rng = random.Random(1000 + depth)
+    ops = [f"d {depth}"]
+    for _ in range(3000):
+        x = rng.random()
+        if x < 0.97:
+            ops.append("b" if x < 0.50 else "e" if x < 0.94 else "r")
+        else:  # everything ended, another depth, one readback through it, back to the depth under test, filled once
+            ops += ["e"] * 16 + [f"d {rng.choice([1, 2, 3, 16])}", "b", "e", f"d {depth}"] + ["b"] * (depth + 1)
+    lines = run(exe, f"ring {len(ops)}\n" + "\n".join(ops) + "\n")
+    assert len(lines) == len(ops)
+    out, cur, restarted, filled = collections.deque(), 2, False, 0
+    for op, line in zip(ops, lines):
+        slot, full, pending, oldest = map(int, line.split())
+        if op == "b":
+            if len(out) == cur:
+                assert slot == -1  # (the driver did not call begin: the ring said full)
+            else:
+                assert 0 <= slot < cur and slot not in out, (op, line, list(out))
+                assert not restarted or slot == 0
+                out.append(slot)
+            restarted = False
+        elif op == "e":
+            assert slot == (out.popleft() if out else -1)
+        elif op == "r":
+            out.clear()
+            restarted = True
+        else:
+            if out:  # (never sent with readbacks outstanding: the 16 ends before it)
+                raise AssertionError("set_depth with readbacks outstanding")
+            cur = int(op.split()[1])
+            restarted = True
+        assert full == int(len(out) == cur) and pending == len(out) and oldest == (out[0] if out else -1), (op, line)
+        filled += full
+    assert filled > 20

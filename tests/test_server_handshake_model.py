@@ -1,6 +1,6 @@
 """The render server's close handshake and stop word as a model (CPU), checked over every interleaving.
 
-The code: hg_mega.hip sv_close / sv_view / sv_wait (device) and hg_runtime.hip server_post_frame / server_stop (host),
+The code: hg_mega.hip sv_close / sv_view / sv_wait (device) and hg_render.hip server_post_frame / server_stop (host),
 DESIGN.md section 4.7b.  Both sides store, then load, with sequentially consistent system-scope atomics, so the model
 interleaves whole steps in program order:
   host, posting frame k:  H1 post word := k + 1;  H2 read the closing word;  if raised: H3 read the close word and take
