@@ -393,12 +393,7 @@ int hg_upload_cubemap(hg_ctx* c, int32_t face_size, int32_t n_mips, const float*
     if (int rc = hg_ctx_flush(c)) return rc;
     if (face_size <= 0 || n_mips <= 0 || n_mips > HG_MAX_CUBE_MIPS || !texels)
         return fail(c, HG_E_INVALID, "bad cubemap shape");
-    uint64_t need = 0;
-    for (int m = 0; m < n_mips; ++m) {
-        c->cube_mip_offset[m] = uint32_t(need / 4);
-        const uint64_t s = std::max(1, face_size >> m);
-        need += 6ull * s * s * 4ull;
-    }
+    const uint64_t need = hg_cube_mip_offsets(face_size, n_mips, c->cube_mip_offset);
     if (need != n_floats) return fail(c, HG_E_INVALID, "cubemap has %zu floats, expected %llu", n_floats,
                                       (unsigned long long)need);
     if (int rc = set_device(c)) return rc;

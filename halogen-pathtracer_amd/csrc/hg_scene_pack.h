@@ -241,6 +241,18 @@ inline int hg_scene_check_limits(const HgSceneIn& in, HgPackError& err) {
     return HG_OK;
 }
 
+// hg_upload_cubemap's mip table: mip m of the [mip][face][y][x][4] chain starts at float4 texel mip_offset[m]; returns the
+// floats of the whole chain (n_mips <= HG_MAX_CUBE_MIPS).  Also called by the test-only probe (hg_devprobe.hip).
+inline uint64_t hg_cube_mip_offsets(int32_t face_size, int32_t n_mips, uint32_t* mip_offset) {
+    uint64_t need = 0;
+    for (int m = 0; m < n_mips; ++m) {
+        mip_offset[m] = uint32_t(need / 4);
+        const uint64_t s = std::max(1, face_size >> m);
+        need += 6ull * s * s * 4ull;
+    }
+    return need;
+}
+
 // ---- the upload decision ----------------------------------------------------------------------------------------------
 enum HgUploadKind { HG_UPLOAD_SKIP, HG_UPLOAD_PARTIAL, HG_UPLOAD_FULL };
 struct HgUploadDecision {

@@ -246,7 +246,9 @@ static void cube_adjacent(int f, int i, int j, int size, int* nf, int* ni, int* 
     *nj = c[1];
 }
 
-void hgo_cube_sample(const hgo_scene* sc, const float dir[3], int32_t level, float rgb[3]) {
+/* info (may be NULL), for the input checks of tests/test_gpu_shading_units.py: the face, the footprint's corner texel
+ * (row * 2 + column, -1 if none), how many of its four texels are off the face, and which (bit row * 2 + column). */
+static void cube_sample(const hgo_scene* sc, const float dir[3], int32_t level, float rgb[3], int32_t info[4]) {
     float x = dir[0], y = dir[1], z = dir[2];
     float ax = x < 0 ? -x : x, ay = y < 0 ? -y : y, az = z < 0 ? -z : z;
     int face;
@@ -280,10 +282,15 @@ void hgo_cube_sample(const hgo_scene* sc, const float dir[3], int32_t level, flo
     const int xs[2] = {(int)fu0, (int)fu0 + 1}, ys[2] = {(int)fv0, (int)fv0 + 1};
     float tex[2][2][3]; /* [row][col][rgb] */
     int corner = -1;    /* footprint texel with both coordinates off the face */
+    int n_off = 0, off_mask = 0;
     for (int r = 0; r < 2; r++) {
         for (int q = 0; q < 2; q++) {
             const int i = xs[q], j = ys[r];
             const int in_i = i >= 0 && i < size, in_j = j >= 0 && j < size;
+            if (!in_i || !in_j) {
+                n_off++;
+                off_mask |= 1 << (r * 2 + q);
+            }
             if (!in_i && !in_j) {
                 corner = r * 2 + q;
                 continue;
@@ -304,6 +311,15 @@ void hgo_cube_sample(const hgo_scene* sc, const float dir[3], int32_t level, flo
         float bot = tex[1][0][c] * (1.0f - fx) + tex[1][1][c] * fx;
         rgb[c] = top * (1.0f - fy) + bot * fy;
     }
+    if (info) {
+        info[0] = face;
+        info[1] = corner;
+        info[2] = n_off;
+        info[3] = off_mask;
+    }
+}
+void hgo_cube_sample(const hgo_scene* sc, const float dir[3], int32_t level, float rgb[3]) {
+    cube_sample(sc, dir, level, rgb, NULL);
 }
 
 /* Exposed for the adjacency unit test (tests/test_cubemap.py). */
@@ -1292,4 +1308,128 @@ void hgo_sphere_accept_batch(const float* in, uint32_t* out, int64_t n) {
         out[2 * i] = h.orientation != 0.0f ? (h.orientation < 0.0f ? 0x80000000u : 0u) : 0xFFFFFFFFu;
         out[2 * i + 1] = hg_f2u(h.rayT);
     }
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Batch forms of the shading half for tests/test_gpu_shading_units.py: the sky, the BSDF pieces, the medium stack and
+ * evaluate_material_hit, each over a tstate set up from the element.  Element layouts: csrc/hg_devprobe.hip (fn 50-58).
+ * ---------------------------------------------------------------------------------------------- */
+/* in: (direction, level as int32), 4 words; rgb: 3 floats; info (may be NULL): cube_sample's 4 words, which only the
+ * oracle can see (the input checks use them; they are not compared with the device) */
+void hgo_sky_batch(const hgo_scene* sc, const float* in, float* rgb, int32_t* info, int64_t n) {
+    for (int64_t i = 0; i < n; i++) {
+        int32_t level;
+        memcpy(&level, in + 4 * i + 3, 4);
+        cube_sample(sc, in + 4 * i, level, rgb + 3 * i, info ? info + 4 * i : NULL);
+    }
+}
+
+/* in: (defaultHDRIMipLevel as int32, accRough), 2 words; out: the level */
+void hgo_sky_level_batch(const float* in, int32_t* out, int64_t n) {
+    hg_params p;
+    memset(&p, 0, sizeof p);
+    for (int64_t i = 0; i < n; i++) {
+        memcpy(&p.defaultHDRIMipLevel, in + 2 * i, 4);
+        out[i] = sky_level(&p, in[2 * i + 1]);
+    }
+}
+
+/* fn 0 lambert_scatter(n, rv), 1 specular_scatter(i, n); in: 6 floats, out: 3 floats */
+void hgo_scatter_batch(int32_t fn, const float* in, float* out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) {
+        const float* e = in + 6 * i;
+        f3 a = v3(e[0], e[1], e[2]), b = v3(e[3], e[4], e[5]);
+        f3 r = fn == 0 ? lambert_scatter(a, b) : specular_scatter(a, b);
+        out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+    }
+}
+
+/* in: (n1, n2, normal, incident, min, max), 10 floats; out: 1 float */
+void hgo_schlick_batch(const float* in, float* out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) {
+        const float* e = in + 10 * i;
+        out[i] = schlick_adjusted(e[0], e[1], v3(e[2], e[3], e[4]), v3(e[5], e[6], e[7]), e[8], e[9]);
+    }
+}
+
+/* in: (incident, normal, n1, n2), 8 floats; out: (direction bits, tir), 4 words */
+void hgo_refract_batch(const float* in, uint32_t* out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) {
+        const float* e = in + 8 * i;
+        int tir = 0;
+        f3 r = refract_tir(v3(e[0], e[1], e[2]), v3(e[3], e[4], e[5]), e[6], e[7], &tir);
+        out[4 * i] = hg_f2u(r.x); out[4 * i + 1] = hg_f2u(r.y); out[4 * i + 2] = hg_f2u(r.z);
+        out[4 * i + 3] = tir ? 1u : 0u;
+    }
+}
+
+/* the initial stack of an element: sp entries, material_medium() of the material indices in the bytes of (lo, hi) */
+static void set_medium_stack(tstate* t, const PackedHalogenMaterial* mats, uint32_t sp, uint32_t lo, uint32_t hi) {
+    const uint64_t s = (uint64_t)lo | ((uint64_t)hi << 32);
+    t->msp = (int)sp;
+    for (int k = 0; k < t->msp; k++) t->mstack[k] = material_medium(&mats[(s >> (8 * k)) & 0xFFu]);
+}
+/* (sp, the materialID of each entry below sp, 0xFFFFFFFF above), 9 words */
+static void get_medium_stack(const tstate* t, uint32_t* out) {
+    out[0] = (uint32_t)t->msp;
+    for (int k = 0; k < 8; k++) out[1 + k] = k < t->msp ? t->mstack[k].materialID : 0xFFFFFFFFu;
+}
+
+/* in: (sp, stack bytes lo, hi, 16 ops), 19 words; an op is kind << 30 | value: kind 1 add_to_medium_stack(material
+ * value), 2 pop_from_medium_stack(id value), 0 nothing; out: the stack after every op, 16 x 9 words */
+void hgo_medium_ops_batch(const PackedHalogenMaterial* mats, const uint32_t* in, uint32_t* out, int64_t n) {
+    tstate t;
+    memset(&t, 0, sizeof t);
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t* e = in + 19 * i;
+        set_medium_stack(&t, mats, e[0], e[1], e[2]);
+        for (int k = 0; k < 16; k++) {
+            const uint32_t kind = e[3 + k] >> 30, val = e[3 + k] & 0x3FFFFFFFu;
+            if (kind == 1u) add_to_medium_stack(&t, material_medium(&mats[val]));
+            else if (kind == 2u) pop_from_medium_stack(&t, val);
+            get_medium_stack(&t, out + (16 * i + k) * 9);
+        }
+    }
+}
+
+/* in: (frame, pixelID, dim_offset; sp, stack bytes lo, hi; ray o, d; hit rayT, orientation, pos, normal, material), 21
+ * words; out: (attenuation, ray o, ray d, the bounceTypes slot incremented, the stack afterwards), 19 words */
+void hgo_evaluate_hit_batch(const PackedHalogenMaterial* mats, int32_t n_mats, const uint32_t* in, uint32_t* out,
+                            int64_t n) {
+    hgo_scene sc;
+    tstate t;
+    memset(&sc, 0, sizeof sc);
+    memset(&t, 0, sizeof t);
+    sc.materials = mats;
+    sc.n_materials = n_mats;
+    t.sc = &sc;
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t* e = in + 21 * i;
+        float f[15];
+        memcpy(f, e + 6, sizeof f);
+        t.frame = e[0];
+        t.pixelID = e[1];
+        t.dim_offset = e[2];
+        set_medium_stack(&t, mats, e[3], e[4], e[5]);
+        ray_t ray = {v3(f[0], f[1], f[2]), v3(f[3], f[4], f[5])};
+        hit_t hit;
+        memset(&hit, 0, sizeof hit);
+        hit.rayT = f[6];
+        hit.orientation = f[7];
+        hit.pos = v3(f[8], f[9], f[10]);
+        hit.normal = v3(f[11], f[12], f[13]);
+        hit.material = e[20];
+        uint32_t bt[3] = {0, 0, 0};
+        f3 att = evaluate_material_hit(&t, &ray, &hit, bt);
+        uint32_t* o = out + 19 * i;
+        o[0] = hg_f2u(att.x); o[1] = hg_f2u(att.y); o[2] = hg_f2u(att.z);
+        o[3] = hg_f2u(ray.o.x); o[4] = hg_f2u(ray.o.y); o[5] = hg_f2u(ray.o.z);
+        o[6] = hg_f2u(ray.d.x); o[7] = hg_f2u(ray.d.y); o[8] = hg_f2u(ray.d.z);
+        o[9] = bt[0] ? 0u : (bt[1] ? 1u : 2u);
+        get_medium_stack(&t, o + 10);
+    }
+}
+
+void hgo_inverted_blackman_harris_batch(const float* in, float* out, int64_t n) {
+    for (int64_t i = 0; i < n; i++) out[i] = hgo_inverted_blackman_harris(in[i]);
 }

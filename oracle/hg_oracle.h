@@ -88,6 +88,16 @@ void hgo_aabb_batch(const float* in, float* out, int64_t n);
 void hgo_rcp_batch(const float* in, float* out, int64_t n);
 void hgo_tri_accept_batch(const float* rays, const HalogenTriangle* tris, uint32_t* out, int64_t n);
 void hgo_sphere_accept_batch(const float* in, uint32_t* out, int64_t n);
+/* Batch forms of the shading half for tests/test_gpu_shading_units.py (hg_devprobe.hip fn 50-58) */
+void hgo_sky_batch(const hgo_scene* scene, const float* in, float* rgb, int32_t* info, int64_t n);
+void hgo_sky_level_batch(const float* in, int32_t* out, int64_t n);
+void hgo_scatter_batch(int32_t fn, const float* in, float* out, int64_t n); /* 0 lambert, 1 specular */
+void hgo_schlick_batch(const float* in, float* out, int64_t n);
+void hgo_refract_batch(const float* in, uint32_t* out, int64_t n);
+void hgo_medium_ops_batch(const PackedHalogenMaterial* materials, const uint32_t* in, uint32_t* out, int64_t n);
+void hgo_evaluate_hit_batch(const PackedHalogenMaterial* materials, int32_t n_materials, const uint32_t* in,
+                            uint32_t* out, int64_t n);
+void hgo_inverted_blackman_harris_batch(const float* in, float* out, int64_t n);
 
 #ifdef __cplusplus
 }
