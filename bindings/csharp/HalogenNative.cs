@@ -193,6 +193,20 @@ public static class HalogenNative
         [Out] float[] outMin, [Out] float[] outMax);
     [DllImport(Lib)] public static extern int hg_pack_triangles(float[] vertices, float[] normals, int nVertices,
         int[] indices, int nTris, [Out] HalogenTriangle[] outTriangles);
+    // Deforming geometry: a mesh's moved triangles (same count, same order) replace its triangles on the device and
+    // every box of its tree is refitted there, topology unchanged; hg_refit_blas does the same to the caller's own copy
+    // of the tree (mesh-relative, root at 0), which the next full upload needs.  hg_scene_readback: a diagnostic copy
+    // of one device scene array (HG_SCENE_*)
+    public const int HG_SCENE_NODES = 0, HG_SCENE_LEAVES = 1, HG_SCENE_TRIS = 2, HG_SCENE_NORMALS = 3,
+        HG_SCENE_MESHES = 4;
+    [DllImport(Lib)] public static extern int hg_refit_blas(HalogenTriangle[] triangles, int nTriangles,
+        [In, Out] BVHEntry[] nodes, int nNodes);
+    [DllImport(Lib)] public static extern int hg_refit_mesh(IntPtr ctx, int meshIndex, HalogenTriangle[] triangles,
+        int nTriangles, ulong geometryGeneration);
+    [DllImport(Lib)] public static extern int hg_refit_mesh_device(IntPtr ctx, int meshIndex, IntPtr dTriangles,
+        int nTriangles, ulong geometryGeneration);
+    [DllImport(Lib)] public static extern int hg_scene_readback(IntPtr ctx, int which, [Out] byte[] dst,
+        UIntPtr capacity, out UIntPtr nBytes);
 
     // Multi-GPU gather (one context per GPU; the render pass keeps one HalogenRenderPass per device and gathers the
     // tiles to the display device once per displayed image).

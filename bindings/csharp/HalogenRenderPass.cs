@@ -383,6 +383,21 @@ public class HalogenRenderPass : ScriptableRenderPass
         cubemapUploaded = cfg.useCubemap;
     }
 
+    // A deformed mesh (not in the reference: skinning, cloth, a morph target; same triangle count and order).
+    // `moved`: the mesh's triangles in the order of its GetPackedTriangles(), `nodes`: its GetBVH() array, which is
+    // refitted in place (hg_refit_blas) so that the component keeps handing out a current tree; every context refits
+    // the mesh on its device under the current geometry generation (the next re-upload stays vouched: small tables
+    // only).  meshIndex: the mesh's position in RayTracingManager.GetMeshList().  The image starts over.  (internal:
+    // the pass's public surface stays the reference's; a deforming component in the same assembly calls it.)
+    internal void RefitMesh(int meshIndex, HalogenTriangle[] moved, BVHEntry[] nodes)
+    {
+        int rc = HalogenNative.hg_refit_blas(moved, moved.Length, nodes, nodes.Length);
+        if (rc != HalogenNative.HG_OK) throw new Exception($"hg_refit_blas failed ({rc})");
+        foreach (IntPtr ctx in contexts)
+            Check(HalogenNative.hg_refit_mesh(ctx, meshIndex, moved, moved.Length, geometryGeneration), "hg_refit_mesh");
+        ClearAccumulation();
+    }
+
     // Index of `material` in the packed list, packing it on first use (PackMaterialToList, RP:524-537: equality by
     // value, so identical materials share one slot).
     uint MaterialSlot(HalogenMaterial material)

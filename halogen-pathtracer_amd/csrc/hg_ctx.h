@@ -4,12 +4,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <map>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "halogen_abi.h"
 #include "hg_layout.h"
+#include "hg_refit_plan.h"
 #include "hg_slot_ring.h"
 
 struct DevBuf {  // a device allocation owned by a context
@@ -33,6 +35,22 @@ struct hg_ctx {
     std::vector<HgDevMesh> dev_meshes;  // the device mesh table of the last upload (partial re-uploads start from it)
     uint64_t scene_uploads = 0, scene_uploads_skipped = 0, scene_uploads_partial = 0, scene_uploads_vouched = 0;
     uint64_t geometry_gen = 0;  // hg_upload_scene_gen: the caller's geometry generation of the last upload (0: none)
+    // Refit (hg_refit_mesh, hg_refit.hip).  Host copies of what the device scene's topology is read from, kept by every
+    // full upload: the two refs of each node record, the leaf table, the bytes of the four geometry arrays; and the local
+    // boxes of each mesh root's two children (a refit replaces its meshes').  geometry_stale: a refit changed the device
+    // since the last full upload, so scene_copy[3] and [4] no longer describe it (hg_upload_decide_refit).  Per refitted
+    // tree (root ref << 32 | triangle offset) its plan on the device, until the next full upload.
+    std::vector<uint32_t> rec_refs, leaf_table;
+    size_t geometry_bytes[4] = {};  // nodes, leaves, triangles, normals as uploaded (the buffers hold at least 16 B)
+    std::vector<HgRootPair> root_pairs;
+    bool geometry_stale = false;
+    struct RefitTree {
+        HgRefitPlan plan;
+        DevBuf list;  // plan.records
+    };
+    std::map<uint64_t, RefitTree> refit_trees;
+    DevBuf refit_in, refit_raw;  // the host-pointer form's triangles; one raw box (6 floats) per record of a tree
+    uint64_t scene_refits = 0;
 
     // cubemap
     DevBuf cube;

@@ -25,6 +25,7 @@
 #include "halogen_abi.h"
 #include "hg_atrous.h"
 #include "hg_host_pool.h"
+#include "hg_refit.h"
 
 namespace {
 
@@ -519,6 +520,55 @@ extern "C" int hg_pack_triangles(const float* V, const float* N, int32_t n_verti
         h.normalA = {N[3 * i0], N[3 * i0 + 1], N[3 * i0 + 2]};
         h.normalB = {N[3 * i1], N[3 * i1 + 1], N[3 * i1 + 2]};
         h.normalC = {N[3 * i2], N[3 * i2 + 1], N[3 * i2 + 2]};
+    }
+    return HG_OK;
+}
+
+// hg_refit_blas: the host twin of the device refit (hg_refit.hip), over the contract of hg_refit.h.  Bottom-up from the
+// root (entry 0): a leaf's raw box from its triangles, an inner entry's the union of its children's; then every reached
+// entry's stored box (the root's without the pad).  Everything is validated before the first box is written: ranges,
+// depth (as hg_upload_scene accepts it) and cycles.  Entries reached along two paths are computed once.
+extern "C" int hg_refit_blas(const HalogenTriangle* tris, int32_t n_tris, BVHEntry* nodes, int32_t n_nodes) {
+    if (!nodes || n_nodes <= 0 || n_tris < 0 || (n_tris && !tris)) return HG_E_INVALID;
+    enum : uint8_t { kNew = 0, kOpen = 1, kDone = 2 };
+    std::vector<uint8_t> state(size_t(n_nodes), kNew);
+    std::vector<HgRawBox> raw;
+    raw.resize(size_t(n_nodes));
+    std::vector<std::pair<uint32_t, uint32_t>> stack{{0u, 0u}};  // (entry, depth)
+    while (!stack.empty()) {
+        const auto [g, depth] = stack.back();
+        const BVHEntry& e = nodes[g];
+        if (state[g] == kNew) {
+            if (depth > HG_REFIT_MAX_DEPTH) return HG_E_UNSUPPORTED;  // deeper than the traversal's stack, or cyclic
+            if (e.triangleCount > 0) {
+                if (uint64_t(e.indexA) + e.triangleCount > uint64_t(n_tris)) return HG_E_INVALID;
+                HgRawBox b = hg_refit_empty();
+                for (uint32_t i = 0; i < e.triangleCount; ++i) hg_refit_add_triangle(b, tris[size_t(e.indexA) + i]);
+                raw[g] = b;
+                state[g] = kDone;
+                stack.pop_back();
+                continue;
+            }
+            if (uint64_t(e.indexA) + 1 >= uint64_t(n_nodes)) return HG_E_INVALID;
+            state[g] = kOpen;
+            for (uint32_t child : {e.indexA + 1, e.indexA}) {
+                if (state[child] == kOpen) return HG_E_UNSUPPORTED;  // a cycle
+                if (state[child] == kNew) stack.push_back({child, depth + 1});
+            }
+        } else {
+            stack.pop_back();
+            if (state[g] != kOpen) continue;
+            raw[g] = hg_refit_union(raw[e.indexA], raw[e.indexA + 1]);
+            state[g] = kDone;
+        }
+    }
+    for (int32_t g = 0; g < n_nodes; ++g) {
+        if (state[size_t(g)] != kDone) continue;
+        float mn[3], mx[3];
+        if (g == 0 && hg_refit_root_is_current_padded(raw[0], nodes[0])) continue;  // (hg_refit.h: the root)
+        hg_refit_stored(raw[size_t(g)], g != 0, mn, mx);
+        nodes[g].boundingCornerA = {mn[0], mn[1], mn[2]};
+        nodes[g].boundingCornerB = {mx[0], mx[1], mx[2]};
     }
     return HG_OK;
 }

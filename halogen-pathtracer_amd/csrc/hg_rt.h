@@ -1,5 +1,5 @@
 // hg_rt.h — what the runtime's translation units (hg_runtime.hip, hg_render.hip, hg_display.hip, hg_query.hip,
-// hg_denoise.hip, hg_comm.hip) share over a context: private to libhalogen_hip.so, none of it in the C-ABI.  The
+// hg_denoise.hip, hg_refit.hip, hg_comm.hip) share over a context: private to libhalogen_hip.so, none of it in the C-ABI.  The
 // helpers are in namespace hgrt (each is defined in the file named beside it); the hg_ctx_* functions are the
 // context's services to hg_comm.hip and to each other.
 #pragma once
@@ -76,5 +76,9 @@ int display_check(hg_ctx* c, int32_t format);
 constexpr int64_t kQueryChunk = int64_t(1) << 20;  // records per launch (and per staging buffer)
 int query_begin(hg_ctx* c);
 int query_params(hg_ctx* c, uint32_t threads, HgKernelParams& kp);
+
+// ---- hg_refit.hip ----
+// Forget the refit plans of the device scene and free their device lists (a full upload lays the records out anew)
+void refit_reset(hg_ctx* c);
 
 }  // namespace hgrt

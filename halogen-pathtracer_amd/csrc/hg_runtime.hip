@@ -1,7 +1,7 @@
 // hg_runtime.hip — the context behind the C-ABI of include/halogen_abi.h: create / destroy, device buffers, scene and
 // cubemap upload, params / resize / tiling / clear, options, counters, self-test, synchronize.  Rendering is
 // hg_render.hip's, display readback hg_display.hip's, ray queries hg_query.hip's, the denoised display
-// hg_denoise.hip's; what they share is declared in hg_rt.h.  Stands in for the ComputeBuffer / RTHandle calls of
+// hg_denoise.hip's, the refit of a deforming mesh hg_refit.hip's; what they share is declared in hg_rt.h.  Stands in for the ComputeBuffer / RTHandle calls of
 // Assets/Scripts/Render Features/HalogenRenderPass.cs (RP:237-508).
 //
 // Error model: every entry point returns HG_OK or a negative HG_E_* code and never aborts; the text of
@@ -252,8 +252,9 @@ void hg_destroy(hg_ctx* c) {
         if (L.stream) (void)hipStreamSynchronize(L.stream);
     for (DevBuf* b : {&c->spheres, &c->meshes, &c->materials, &c->nodes, &c->leaves, &c->tris, &c->normals, &c->cube,
                       &c->acc, &c->counters_dev, &c->spill, &c->lost, &c->query_in, &c->query_out, &c->guide0,
-                      &c->guide1, &c->denoise_work[0], &c->denoise_work[1]})
+                      &c->guide1, &c->denoise_work[0], &c->denoise_work[1], &c->refit_in, &c->refit_raw})
         release(*b);
+    refit_reset(c);
     // The trace streams first, the server's stream after them: destroyed before them, the next hipStreamDestroy of a
     // plain trace stream hung in round 5 (DESIGN.md section 4.7 has what the analysis found)
     for (hg_ctx::TraceLane& L : c->lanes) {
@@ -324,6 +325,20 @@ int commit_scene(hg_ctx* c, const HgSceneIn& in, HgScenePack& pack, HgUploadDeci
         c->stack_depth = pack.stack_depth;
         c->n_tris = in.n_tris;
         c->n_nodes = in.n_nodes;
+        // what a refit reads of this layout (hg_refit.hip); the caller's arrays describe the device again
+        refit_reset(c);
+        c->rec_refs.resize(pack.rec.size() / 2);
+        for (size_t r = 0; r < pack.rec.size() / 4; ++r) {
+            std::memcpy(&c->rec_refs[2 * r], &pack.rec[4 * r].w, 4);
+            std::memcpy(&c->rec_refs[2 * r + 1], &pack.rec[4 * r + 1].w, 4);
+        }
+        c->leaf_table.resize(pack.leaf.size() * 2);
+        std::memcpy(c->leaf_table.data(), pack.leaf.data(), pack.leaf.size() * sizeof(uint2));
+        const size_t bytes[4] = {pack.rec.size() * sizeof(float4), pack.leaf.size() * sizeof(uint2),
+                                 pack.t9.size() * sizeof(float), pack.nrm.size() * sizeof(float4)};
+        std::memcpy(c->geometry_bytes, bytes, sizeof bytes);
+        hg_root_pairs(in, c->root_pairs);
+        c->geometry_stale = false;
     }
     c->geometry_gen = geometry_generation;
     c->n_spheres = in.n_spheres;
@@ -352,8 +367,10 @@ int hg_upload_scene_gen(hg_ctx* c, uint64_t geometry_generation, const HalogenSp
     const HgSceneIn in{spheres, n_spheres, meshes, n_meshes, materials, n_materials, tris, n_tris, blas, n_nodes};
     HgPackError err;
     if (hg_scene_check_limits(in, err)) return fail(c, err);
-    const HgUploadDecision d = hg_upload_decide(c->has_scene, c->scene_copy, c->geometry_gen, c->dev_meshes.size(), in,
-                                                geometry_generation);
+    const bool stale = c->geometry_stale;  // refitted since the last full upload (hg_refit.hip)
+    const HgUploadDecision d = hg_upload_decide_refit(c->has_scene, stale, c->scene_copy, c->geometry_gen,
+                                                      c->dev_meshes.size(), c->n_tris, c->n_nodes, in,
+                                                      geometry_generation);
     if (d.kind == HG_UPLOAD_SKIP) {
         c->scene_uploads_skipped++;
         c->scene_uploads_vouched += d.vouched ? 1u : 0u;
@@ -367,7 +384,9 @@ int hg_upload_scene_gen(hg_ctx* c, uint64_t geometry_generation, const HalogenSp
     const bool partial = d.kind == HG_UPLOAD_PARTIAL;
     HgScenePack pack;
     if (hg_pack_spheres_materials(in, pack, err)) return fail(c, err);
-    if (partial && hg_pack_mesh_table(in, c->dev_meshes, pack, err)) return fail(c, err);
+    if (partial && (stale ? hg_pack_mesh_table_kept(in, c->dev_meshes, c->root_pairs, pack, err)
+                          : hg_pack_mesh_table(in, c->dev_meshes, pack, err)))
+        return fail(c, err);
     if (int rc = set_device(c)) return rc;
     if (int rc = quiesce(c)) return rc;  // no trace in flight reads the buffers replaced below
     c->has_scene = false;

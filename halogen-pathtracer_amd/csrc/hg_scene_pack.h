@@ -2,6 +2,8 @@
 // the validation of the caller's arrays and the layout of the device scene (hg_layout.h).  Plain functions of plain
 // arrays and nothing of HIP, so plain g++ compiles this header: tests/test_scene_pack.py and host/asan_scene_pack.cpp
 // (AddressSanitizer + UBSan) run it with no GPU.  hg_runtime.hip keeps the HIP calls and the context's bookkeeping.
+// Also here: what changes in those decisions once a mesh was refitted on the device (hg_refit.hip), tested by
+// tests/test_refit.py and host/asan_refit.cpp.
 //
 // An error is the HG_E_* code plus its text (HgPackError); hg_runtime.hip hands both to fail().
 #pragma once
@@ -34,9 +36,12 @@ static_assert(sizeof(uint2) == HG_UINT2_BYTES && alignof(uint2) == HG_UINT2_BYTE
 
 #include "hg_host_pool.h"
 #include "hg_layout.h"
+#include "hg_refit.h"
+#include "hg_refit_plan.h"
 
 constexpr uint32_t kMaxStack = 64;  // LDS stack entries per lane; BLAS depth must be <= kMaxStack - 2
 constexpr int kHostThreads = 16;    // host threads of hg_upload_scene's compare / repack (the GPU box's CPU share)
+static_assert(HG_REFIT_MAX_DEPTH == kMaxStack - 2, "hg_refit_blas accepts the depths hg_pack_geometry accepts");
 
 struct HgPackError {
     int code = HG_OK;
@@ -348,6 +353,76 @@ inline int hg_pack_mesh_table(const HgSceneIn& in, const std::vector<HgDevMesh>&
         fill_mesh_record(in.meshes[mi], in.blas, dm[mi]);
     }
     return HG_OK;
+}
+
+// ---- after a refit (hg_refit_mesh, hg_refit.hip) ------------------------------------------------------------------------
+// The local boxes of every mesh root's two children, as the caller's BVH entries hold them (a full upload keeps them on
+// the context; a refit replaces those of the meshes it refitted)
+inline void hg_root_pairs(const HgSceneIn& in, std::vector<HgRootPair>& out) {
+    out.assign(size_t(in.n_meshes), HgRootPair{});
+    for (int mi = 0; mi < in.n_meshes; ++mi) {
+        const uint32_t off = in.meshes[mi].accelerationBufferOffset;
+        if (in.blas[off].triangleCount != 0) continue;
+        const BVHEntry* ab = &in.blas[off + in.blas[off].indexA];
+        for (int k = 0; k < 2; ++k) {
+            std::memcpy(&out[size_t(mi)].box[6 * k], &ab[k].boundingCornerA, 12);
+            std::memcpy(&out[size_t(mi)].box[6 * k + 3], &ab[k].boundingCornerB, 12);
+        }
+    }
+}
+
+// set_cull_boxes from kept root-child boxes instead of the caller's BVH entries; `prev` tells whether the root is inner
+inline void set_cull_boxes_kept(const HalogenMeshData& m, const HgRootPair& kept, HgDevMesh& dm) {
+    const bool inner = !(dm.root_ref & HG_LEAF_BIT);
+    dm.cullable = 0;
+    dm.cull_a_lo = dm.cull_a_hi = dm.cull_b_lo = dm.cull_b_hi = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!inner) return;
+    BVHEntry ab[2] = {};
+    for (int k = 0; k < 2; ++k) {
+        std::memcpy(&ab[k].boundingCornerA, &kept.box[6 * k], 12);
+        std::memcpy(&ab[k].boundingCornerB, &kept.box[6 * k + 3], 12);
+    }
+    if (mesh_cull_boxes(m.worldToLocal, ab[0], ab[1], dm)) dm.cullable = 1;
+    else dm.cull_a_lo = dm.cull_a_hi = dm.cull_b_lo = dm.cull_b_hi = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// hg_pack_mesh_table for a context whose geometry was refitted: the caller's BVH entries are not read
+inline int hg_pack_mesh_table_kept(const HgSceneIn& in, const std::vector<HgDevMesh>& prev,
+                                   const std::vector<HgRootPair>& kept, HgScenePack& out, HgPackError& err) {
+    std::vector<HgDevMesh>& dm = out.dm;
+    dm = prev;
+    for (int mi = 0; mi < in.n_meshes; ++mi) {
+        if (int rc = check_mesh_material(in, mi, err)) return rc;
+        const HalogenMeshData& m = in.meshes[mi];
+        std::memcpy(dm[size_t(mi)].w2l, m.worldToLocal.m, sizeof dm[size_t(mi)].w2l);
+        dm[size_t(mi)].material = m.materialIndex;
+        set_cull_boxes_kept(m, kept[size_t(mi)], dm[size_t(mi)]);
+    }
+    return HG_OK;
+}
+
+// hg_upload_decide for a context that may have been refitted.  `stale`: a refit changed the device's triangles and
+// boxes since the last full upload, so the retained copies of the triangles and BVH entries (copy[3], copy[4]) no
+// longer describe the device and nothing may be compared against them.  Then an upload is vouched only when its
+// generation is non-zero and the refit's, and the triangle count, the node count and every mesh's two offsets are the
+// device's: it decides skip or partial from the three small tables alone.  Every other upload after a refit is a full
+// upload from the caller's arrays (which the caller kept current, hg_refit_blas): never skip, never partial.
+inline HgUploadDecision hg_upload_decide_refit(bool has_scene, bool stale, const std::vector<uint8_t> (&copy)[5],
+                                               uint64_t last_gen, size_t n_dev_meshes, int32_t dev_tris,
+                                               int32_t dev_nodes, const HgSceneIn& in, uint64_t generation) {
+    if (!has_scene || !stale) return hg_upload_decide(has_scene, copy, last_gen, n_dev_meshes, in, generation);
+    bool vouched = generation != 0 && generation == last_gen && in.n_tris == dev_tris && in.n_nodes == dev_nodes &&
+                   size_t(in.n_meshes) == n_dev_meshes && copy[1].size() == in.bytes(1);
+    for (int mi = 0; vouched && mi < in.n_meshes; ++mi) {
+        const HalogenMeshData& o = reinterpret_cast<const HalogenMeshData*>(copy[1].data())[mi];
+        vouched = o.triangleBufferOffset == in.meshes[mi].triangleBufferOffset &&
+                  o.accelerationBufferOffset == in.meshes[mi].accelerationBufferOffset;
+    }
+    if (!vouched) return {HG_UPLOAD_FULL, false};
+    bool same = true;
+    for (int k = 0; k < 3; ++k)
+        same = same && copy[k].size() == in.bytes(k) && (!in.bytes(k) || !std::memcmp(copy[k].data(), in.src(k), in.bytes(k)));
+    return {same ? HG_UPLOAD_SKIP : HG_UPLOAD_PARTIAL, true};
 }
 
 // ---- the geometry of a full rebuild: triangles, BLAS validation, device layout, mesh table -----------------------------

@@ -159,7 +159,12 @@ EXPORTS = [
     "hg_comm_unique_id", "hg_comm_init_rank", "hg_comm_init_all", "hg_comm_gather", "hg_comm_synchronize",
     "hg_comm_readback", "hg_comm_readback_begin", "hg_comm_readback_end", "hg_comm_set_timeout_ms", "hg_comm_transport", "hg_comm_last_error", "hg_comm_destroy",
     "hg_comm_assemble_host",
+    "hg_refit_blas", "hg_refit_mesh", "hg_refit_mesh_device", "hg_scene_readback",
 ]
+# hg_scene_readback: the device scene's arrays (layouts private to the library, csrc/hg_layout.h)
+HG_SCENE_NODES, HG_SCENE_LEAVES, HG_SCENE_TRIS, HG_SCENE_NORMALS, HG_SCENE_MESHES = 0, 1, 2, 3, 4
+SCENE_ARRAYS = {"nodes": HG_SCENE_NODES, "leaves": HG_SCENE_LEAVES, "tris": HG_SCENE_TRIS,
+                "normals": HG_SCENE_NORMALS, "meshes": HG_SCENE_MESHES}
 HG_COMM_ID_BYTES = 128
 HG_COMM_RCCL, HG_COMM_PEER = 1, 2
 HG_SELFTEST_RCP = 1
@@ -232,6 +237,10 @@ def lib() -> C.CDLL:
         "hg_comm_transport": (C.c_int, [P]),
         "hg_comm_last_error": (C.c_char_p, [P]),
         "hg_comm_destroy": (None, [P]),
+        "hg_refit_blas": (C.c_int, [P, i32, P, i32]),
+        "hg_refit_mesh": (C.c_int, [P, i32, P, i32, C.c_uint64]),
+        "hg_refit_mesh_device": (C.c_int, [P, i32, P, i32, C.c_uint64]),
+        "hg_scene_readback": (C.c_int, [P, i32, P, sz, C.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -439,6 +448,43 @@ class Context:
                     "hg_camera_rays")
         return rays
 
+    # --- deforming geometry (hg_refit_mesh, hg_refit_mesh_device, hg_scene_readback) ----------------------------------
+    def refit_mesh(self, mesh_index: int, triangles, generation: int = 0) -> None:
+        """Replace the triangles of mesh `mesh_index` of the uploaded scene and refit its BVH boxes on the device,
+        topology unchanged.  triangles on the host: a ctypes array of HalogenTriangle, or a numpy array of 72 bytes per
+        triangle ((n, 18) float32).  triangles as a contiguous (n, 18) float32 torch tensor on the context's device: read
+        in place through the device entry point.  generation: the geometry generation the next (vouched) upload_scene
+        will carry.  The accumulation is not cleared."""
+        if hasattr(triangles, "data_ptr") and not isinstance(triangles, np.ndarray):
+            import torch
+
+            if not (triangles.is_cuda and triangles.device.index == self.device and triangles.dtype == torch.float32 and
+                    triangles.dim() == 2 and triangles.shape[1] == 18 and triangles.is_contiguous()):
+                raise ValueError(f"device triangles must be a contiguous (n, 18) float32 tensor on cuda:{self.device}")
+            torch.cuda.current_stream(triangles.device).synchronize()  # the triangles are complete before the call
+            self._check(lib().hg_refit_mesh_device(self._h, int(mesh_index), C.c_void_p(triangles.data_ptr()),
+                                                   triangles.shape[0], int(generation)), "hg_refit_mesh_device")
+            return
+        if isinstance(triangles, np.ndarray):
+            a = np.ascontiguousarray(triangles)
+            if a.nbytes % C.sizeof(HalogenTriangle):
+                raise ValueError("triangles must hold 72 bytes per triangle")
+            n, keep = a.nbytes // C.sizeof(HalogenTriangle), a
+        else:
+            n, keep = len(triangles), triangles
+        self._check(lib().hg_refit_mesh(self._h, int(mesh_index), _ptr(keep), n, int(generation)), "hg_refit_mesh")
+
+    def scene_readback(self, which) -> np.ndarray:
+        """A diagnostic copy of one array of the device scene ("nodes", "leaves", "tris", "normals", "meshes" or an
+        HG_SCENE_* value) as bytes: two contexts hold the same scene exactly when all five are equal."""
+        w = SCENE_ARRAYS[which] if isinstance(which, str) else int(which)
+        n = C.c_size_t(0)
+        self._check(lib().hg_scene_readback(self._h, w, None, 0, C.byref(n)), "hg_scene_readback")
+        out = np.zeros(n.value, dtype=np.uint8)
+        self._check(lib().hg_scene_readback(self._h, w, _ptr(out) if n.value else None, n.value, C.byref(n)),
+                    "hg_scene_readback")
+        return out
+
     # --- denoised display (hg_update_guides, hg_readback_guides; readback_begin(denoise=...)) -------------------------
     def update_guides(self, params: HgParams, frame_count: int) -> None:
         """Trace the guide images (first-hit normal + distance, albedo + kind) of the camera rays frame `frame_count`
@@ -591,6 +637,15 @@ def denoise_host(rgba: np.ndarray, guide0: np.ndarray, guide1: np.ndarray, param
     if rc != HG_OK:
         raise HalogenError(f"hg_denoise_host failed ({rc}): bad size or parameters", rc)
     return out
+
+
+def refit_blas(triangles, nodes) -> None:
+    """hg_refit_blas: rewrite, in place, the boxes of one mesh's tree (`nodes`: a ctypes array of BVHEntry, root at 0)
+    from its triangles in tree order (a ctypes array of HalogenTriangle), topology unchanged: what the device holds after
+    Context.refit_mesh of the same triangles.  Needs no GPU."""
+    rc = lib().hg_refit_blas(_ptr(triangles), len(triangles), _ptr(nodes), len(nodes))
+    if rc != HG_OK:
+        raise HalogenError(f"hg_refit_blas failed ({rc}): a range, the depth or a cycle of the tree", rc)
 
 
 def pack_display(rgba: np.ndarray, fmt: int) -> np.ndarray:

@@ -177,6 +177,7 @@ class HalogenRenderPass:
         # hg_upload_scene_gen's geometry generation: bumped whenever the scene's meshes (cache token, triangle and node
         # counts, in order) differ from the last upload's, so a camera move's re-upload compares only the small arrays
         self._geometry = (None, 0)
+        self._deform_serials = []  # each mesh's deform_serial at the last upload (a change: refit, not rebuild)
         self.rank, self.n_ranks = 0, 1
         # display (RP:343-347): the reference's camera target is R11G11B10 float (URP-HighFidelity.asset:26-27)
         self.display_format = abi.HG_DISPLAY_R11G11B10F
@@ -219,8 +220,16 @@ class HalogenRenderPass:
         generation = 0  # a bare PackedScene: every array compared
         if hasattr(scene, "meshes") and hasattr(scene, "pack"):
             sig = tuple((m.cache_token, m.triangle_count, len(m.bvh)) for m in scene.meshes)
+            serials = [m.deform_serial for m in scene.meshes]
             if sig != self._geometry[0]:
                 self._geometry = (sig, self._geometry[1] + 1)
+            else:
+                # deformed meshes (RayTracingMesh.deform: same topology, moved vertices): their triangles and BVH boxes
+                # are refitted on the device under the current generation, so the upload below stays vouched
+                for i, m in enumerate(scene.meshes):
+                    if serials[i] != self._deform_serials[i]:
+                        self.ctx.refit_mesh(i, m.packed_triangles, self._geometry[1])
+            self._deform_serials = serials
             generation = self._geometry[1]
         self.ctx.upload_scene(packed, generation)
         self._guides_dirty = True
@@ -244,6 +253,10 @@ class HalogenRenderPass:
             self.ClearAccumulation()
         self._prior_pose = pose
         self._last_scene, self._last_camera = scene, camera
+        if hasattr(scene, "meshes") and hasattr(scene, "pack") and not self.ObjectBuffersDirty and \
+                [m.deform_serial for m in scene.meshes] != self._deform_serials:
+            self._guides_dirty = True
+            self.ClearAccumulation()  # a mesh was deformed: the image starts over, the buffers are refreshed
         if self.ObjectBuffersDirty:
             self.UpdateObjectBuffers(scene)
             self.ObjectBuffersDirty = False

@@ -116,6 +116,7 @@ class RayTracingMesh:
         self.material = material if material is not None else HalogenMaterial.default()
         self.max_hierarchy_depth = int(max_hierarchy_depth)
         self.blas_builder = _blas_builder
+        self.deform_serial = 0  # deform() calls since the geometry was cached
         self._cache()
 
     def _cache(self):
@@ -148,6 +149,26 @@ class RayTracingMesh:
                                  self.triangles.ctypes.data, n_tris, C.cast(self.packed_triangles, C.c_void_p))
         if rc != 0:
             raise abi.HalogenError(f"hg_pack_triangles failed for {self.name}: {rc}")
+
+    def deform(self, vertices, normals=None) -> None:
+        """Move the vertices (same count; skinning, cloth, a morph target) and keep the topology: the triangles are
+        repacked through the index list the BLAS build already permuted, and the BLAS is refitted on the host
+        (hg_refit_blas: every box from the moved triangles, the tree as it was), so pack() is always current.  The
+        cache token stays (the geometry generation does not change); deform_serial tells the pass to refit the device
+        (Context.refit_mesh) instead of rebuilding.  A refitted tree is valid for any deformation and as tight as the
+        builder's boxes, but its split planes are the rest pose's: large deformations trace slower than a rebuild."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        n = self.normals if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if v.shape != self.vertices.shape or n.shape != v.shape:
+            raise ValueError("deform keeps the vertex count")
+        self.vertices, self.normals = v, n
+        rc = abi.lib().hg_pack_triangles(v.ctypes.data, n.ctypes.data, len(v), self.triangles.ctypes.data,
+                                         len(self.triangles), C.cast(self.packed_triangles, C.c_void_p))
+        if rc != 0:
+            raise abi.HalogenError(f"hg_pack_triangles failed for {self.name}: {rc}")
+        if len(self.triangles):
+            abi.refit_blas(self.packed_triangles, self.bvh)
+        self.deform_serial += 1
 
     @property
     def triangle_count(self) -> int:

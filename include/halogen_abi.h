@@ -13,7 +13,8 @@
  *     - DispatchCompute + accumulation   RP:324-347, RP:406      -> hg_render (trace + fused accumulate)
  *       blit (AccumulationShader.shader:27-34)
  *     - Dispose / Release                RP:410-423              -> hg_destroy
- *   plus what the reference never had: readback, counters, error text, multi-GPU tiling.
+ *   plus what the reference never had: readback, counters, error text, multi-GPU tiling, ray queries, the denoised
+ *   display, and deforming meshes (hg_refit_mesh: a device refit of one mesh's triangles and BVH boxes).
  *
  * The host structs below are byte-identical to the reference's C# blittable structs
  * (RP:10-76, strides from Marshal.SizeOf at RP:163-167): a C# caller passes its List<T>.ToArray()
@@ -316,6 +317,52 @@ int hg_upload_scene_gen(hg_ctx* ctx, uint64_t geometry_generation,
                         const PackedHalogenMaterial* materials, int32_t n_materials,
                         const HalogenTriangle* triangles, int32_t n_triangles,
                         const BVHEntry* blas, int32_t n_nodes);
+
+/* ----------------------------------------------------------------------------------------------
+ * Deforming geometry (not in the reference, which rebuilds a mesh's BVH on the host): a REFIT keeps a tree's topology
+ * and recomputes every box from the mesh's moved triangles — a skinned character, cloth, a morph target, a vertex
+ * animation.  The boxes are exactly BVHGenerator's arithmetic on the same triangle sets (csrc/hg_refit.h has the
+ * contract: raw min / max bottom-up, the Bounds round trip and the thin-box pad per entry, the root without the pad),
+ * and the host twin hg_refit_blas and the device agree bit for bit.  Vertex count, triangle count and triangle order
+ * must not change; vertices are assumed finite and are not checked (as hg_upload_scene does not check them).
+ *
+ * hg_refit_mesh / hg_refit_mesh_device replace the triangles of mesh `mesh_index` of the uploaded scene (`n_tris`
+ * HalogenTriangle in the mesh's own tree order, as they sit in the uploaded triangle array from its
+ * triangleBufferOffset) and recompute, on the device, the mesh's triangle and normal records, every box of its tree and
+ * the exact-cull boxes of every mesh that uses the tree (meshes that share both buffer offsets are instances and are
+ * refitted together, each with its own matrix).  Afterwards the device holds, byte for byte, what a fresh context holds
+ * after hg_upload_scene of the caller's arrays with these triangles and hg_refit_blas's boxes.  Like an upload the call
+ * launches the held frames, stops a render server, waits for the context's streams and returns with the device ready.
+ * It does not clear the accumulation (hg_clear_accumulation is the caller's) and keeps the tile cost order (the
+ * geometry moved; the image is similar); guide images (hg_update_guides) become invalid.  The device form takes 4-byte
+ * aligned device memory on the context's device (16-byte aligned is read faster), complete before the call.
+ * Refused, with text in hg_last_error and the scene untouched: no scene (HG_E_NOSCENE); mesh_index out of range, a null
+ * array, n_tris smaller than the tree's leaves reach or past the scene's triangle count (HG_E_INVALID); a mesh whose
+ * triangle range overlaps that of a mesh with another tree, which would go stale (HG_E_UNSUPPORTED).
+ *
+ * After a refit the library's retained copies of the triangles and BVH entries no longer describe the device, so the
+ * upload rule changes until the next full upload: hg_upload_scene_gen under the refit's non-zero `geometry_generation`,
+ * with unchanged triangle count, node count and mesh offsets, is vouched (skip or partial from the three small tables;
+ * a partial upload's cull boxes come from the refitted tree, not from the caller's `blas`); EVERY other upload is a full
+ * upload of the caller's arrays, which the caller must have kept current (hg_refit_blas on its copy of the tree).
+ *
+ * hg_refit_blas: the host twin.  One mesh's tree (root at entry 0, mesh-relative indices, any builder's) and its
+ * triangles in tree order; rewrites boundingCornerA/B of every entry reachable from the root and nothing else (a root
+ * that already is the padded box of its triangles, as hg_build_blas_sah makes it, is kept: a current tree comes back
+ * unchanged whichever builder made it; any other root is rounded without the pad).  Checks
+ * ranges (HG_E_INVALID), depth and cycles (HG_E_UNSUPPORTED) before it writes anything.
+ *
+ * hg_scene_readback: a diagnostic copy of one array of the device scene (HG_SCENE_*: node records, leaf table,
+ * triangles, normals, mesh records; layouts private to the library, csrc/hg_layout.h) for tests that compare device
+ * states.  *n_bytes (optional) gets the array's size; dst NULL asks for the size only.
+ * -------------------------------------------------------------------------------------------- */
+enum { HG_SCENE_NODES = 0, HG_SCENE_LEAVES = 1, HG_SCENE_TRIS = 2, HG_SCENE_NORMALS = 3, HG_SCENE_MESHES = 4 };
+int hg_refit_blas(const HalogenTriangle* triangles, int32_t n_triangles, BVHEntry* nodes, int32_t n_nodes);
+int hg_refit_mesh(hg_ctx* ctx, int32_t mesh_index, const HalogenTriangle* triangles, int32_t n_triangles,
+                  uint64_t geometry_generation);
+int hg_refit_mesh_device(hg_ctx* ctx, int32_t mesh_index, const void* d_triangles, int32_t n_triangles,
+                         uint64_t geometry_generation);
+int hg_scene_readback(hg_ctx* ctx, int32_t which, void* dst, size_t capacity, size_t* n_bytes);
 
 /* Environment cubemap (EnvironmentCubemap, HalgoenCompute.compute:48): RGBA32F texels, layout
  * [mip][face][y][x][4], faces +X,-X,+Y,-Y,+Z,-Z, mip m is max(1, face_size >> m) square.

@@ -236,6 +236,23 @@ class HalogenRenderPass {
         }
     }
 
+    // A deformed mesh (not in the reference: skinning, cloth, a morph target; same triangle count and order).  The
+    // mesh's slice of sc.triangles holds the moved triangles already.  Its slice of sc.blas is refitted in place on the
+    // host (hg_refit_blas), so the buffers stay what a full upload needs, and the device is refitted under the buffers'
+    // generation (hg_refit_mesh), so the next UpdateObjectBuffers is still vouched: no rebuild, no 90-MB upload.  The
+    // image starts over.  mesh: the index in sc.meshes; n_triangles / n_nodes: the lengths of its two slices.
+    void RefitMesh(SceneBuffers& sc, int32_t mesh, int32_t n_triangles, int32_t n_nodes) {
+        if (mesh < 0 || size_t(mesh) >= sc.meshes.size()) throw std::runtime_error("RefitMesh: mesh out of range");
+        const HalogenMeshData& m = sc.meshes[size_t(mesh)];
+        if (n_triangles < 0 || n_nodes < 0 || size_t(m.triangleBufferOffset) + size_t(n_triangles) > sc.triangles.size() ||
+            size_t(m.accelerationBufferOffset) + size_t(n_nodes) > sc.blas.size())
+            throw std::runtime_error("RefitMesh: slice out of range");
+        const HalogenTriangle* tris = sc.triangles.data() + m.triangleBufferOffset;
+        check(hg_refit_blas(tris, n_triangles, sc.blas.data() + m.accelerationBufferOffset, n_nodes), "hg_refit_blas");
+        check(hg_refit_mesh(ctx_, mesh, tris, n_triangles, sc.geometry_generation), "hg_refit_mesh");
+        ClearAccumulation();
+    }
+
     // RP:270-357.  One Execute per frame in the reference; n_frames > 1 runs that many frames in one dispatch with
     // the identical per-frame semantics (FrameCount advancing, the same blend) as long as nothing changes between.
     void Execute(const SceneBuffers& scene, const Camera& camera, int32_t n_frames = 1) {
