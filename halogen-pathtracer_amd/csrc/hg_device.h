@@ -372,7 +372,9 @@ __device__ __forceinline__ bool tri_accept(f3 lo, f3 ld, float4 a, float4 b, flo
 }
 
 // Traversal stack: the first kLds entries of each lane live in LDS ([depth][lane], conflict-free), deeper entries
-// (rare: the BLAS depth cap is 32) spill to a per-lane global column, so the LDS footprint does not cap occupancy.
+// (rare for the builders' trees, whose depth cap is 32; an uploaded tree may be 62 levels deep, stack_depth 64:
+// hg_pack_geometry, tests/tree_cases.py chain62) spill to a per-lane global column, so the LDS footprint does not cap
+// occupancy.
 // The LDS part is addressed through the address-space-3 array itself (a generic pointer here would turn every
 // access into a flat instruction).
 extern __shared__ __attribute__((aligned(16))) uint32_t hg_lds_stack[];

@@ -150,9 +150,16 @@ typedef struct {
     uint32_t materialID;
 } medium_t;
 
+/* What a ray query reports beyond hit_t (hgo_intersect_batch): which primitive the intersection loops accepted last */
+typedef struct {
+    uint32_t kind, object, primitive; /* HG_HIT_*; mesh or sphere index; triangle index in the scene's triangle array */
+    float u, v;
+} query_t;
+
 typedef struct {
     const hgo_scene* sc;
     const hg_params* p;
+    query_t* q;            /* NULL in a render; a ray query's record of the accepted primitive */
     uint32_t frame;        /* FrameCount as uint */
     uint32_t dim_offset;   /* SobolDimensionOffset */
     uint32_t pixelID;      /* u32_hash(pixel index) */
@@ -445,6 +452,10 @@ static void scene_isect_spheres(tstate* t, const ray_t* ray, hit_t* closest) {
             if (h.rayT < closestDistance && h.rayT > 0.0001f) {
                 *closest = h;
                 closestDistance = h.rayT;
+                if (t->q) {
+                    t->q->kind = HG_HIT_SPHERE;
+                    t->q->object = (uint32_t)i;
+                }
             }
         }
     }
@@ -578,19 +589,27 @@ static void scene_isect_meshes(tstate* t, const ray_t* ray, hit_t* closestHit) {
         nrm = normalize3(vec_mul_mat(nrm, &md->worldToLocal));
         closestHit->normal = nrm;
         closestHit->pos = add3(ray->o, muls(ray->d, closest.rayT));
+        if (t->q) {
+            t->q->kind = HG_HIT_MESH;
+            t->q->object = closest.mesh;
+            t->q->primitive = md->triangleBufferOffset + closest.tri;
+            t->q->u = closest.u;
+            t->q->v = closest.v;
+        }
     }
 }
 
-/* get_ray_intersection, :474-485 */
-static hit_t get_ray_intersection(tstate* t, const ray_t* ray) {
+/* get_ray_intersection, :474-485, with the closest distance seeded by the caller (the reference seeds 1.#INF) */
+static hit_t get_ray_intersection_from(tstate* t, const ray_t* ray, float seed) {
     hit_t h;
     memset(&h, 0, sizeof h);
-    h.rayT = HG_INF;
+    h.rayT = seed;
     t->cnt.rays++;
     scene_isect_spheres(t, ray, &h);
     scene_isect_meshes(t, ray, &h);
     return h;
 }
+static hit_t get_ray_intersection(tstate* t, const ray_t* ray) { return get_ray_intersection_from(t, ray, HG_INF); }
 
 /* ------------------------------------------------------------------------------------------------
  * BSDF and medium stack — :491-817
@@ -997,6 +1016,69 @@ int hgo_render(const hgo_scene* scene, const hg_params* params, int32_t n_frames
     free(jobs);
     free(th);
     return 0;
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * Ray queries (include/halogen_abi.h "Ray queries over the uploaded scene"): get_ray_intersection for a caller's rays
+ * and get_ray for a caller's pixels, one after the other on the calling thread.
+ * ---------------------------------------------------------------------------------------------- */
+void hgo_intersect_batch(const hgo_scene* scene, const hg_ray* rays, hg_ray_hit* hits, int64_t n) {
+    hg_params p;
+    memset(&p, 0, sizeof p);
+    p.viewParameters.w = HG_INF; /* a query has no far plane */
+    p.bufferCounts.x = (float)scene->n_spheres; /* ... and answers for every sphere and mesh of the scene */
+    p.bufferCounts.y = (float)scene->n_meshes;
+    tstate t;
+    memset(&t, 0, sizeof t);
+    t.sc = scene;
+    t.p = &p;
+    for (int64_t i = 0; i < n; i++) {
+        const hg_ray* r = &rays[i];
+        const ray_t ray = {v3(r->origin.x, r->origin.y, r->origin.z), v3(r->direction.x, r->direction.y, r->direction.z)};
+        query_t q;
+        memset(&q, 0, sizeof q);
+        t.q = &q;
+        const hit_t h = get_ray_intersection_from(&t, &ray, r->t_max);
+        hg_ray_hit* o = &hits[i];
+        memset(o, 0, sizeof *o);
+        o->t = HG_INF; /* a miss: +inf whatever t_max was, everything else 0 */
+        if (q.kind == HG_HIT_NONE) continue;
+        o->t = h.rayT;
+        o->kind = q.kind;
+        o->object = q.object;
+        o->material = h.material;
+        o->orientation = h.orientation;
+        o->normal.x = h.normal.x;
+        o->normal.y = h.normal.y;
+        o->normal.z = h.normal.z;
+        if (q.kind == HG_HIT_MESH) {
+            o->primitive = q.primitive;
+            o->u = q.u;
+            o->v = q.v;
+        }
+    }
+}
+
+void hgo_camera_rays(const hg_params* params, int32_t frame_count, const int32_t* pixels_xy, hg_ray* rays, int64_t n) {
+    pthread_once(&g_sobol_once, build_sobol_table);
+    tstate t;
+    memset(&t, 0, sizeof t);
+    t.p = params;
+    t.frame = (uint32_t)frame_count;
+    const float W = params->screenParameters.x, H = params->screenParameters.y;
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t x = (uint32_t)pixels_xy[2 * i], y = (uint32_t)pixels_xy[2 * i + 1];
+        /* the head of halogen_compute_pixel, :1023-1033 */
+        const float ndcx = ((float)x / W) * 2.0f - 1.0f, ndcy = ((float)y / H) * 2.0f - 1.0f;
+        t.pixelID = hgo_pcg_hash(x + y * (uint32_t)W);
+        t.dim_offset = 0;
+        const ray_t r = get_ray(&t, ndcx, ndcy);
+        hg_ray* o = &rays[i];
+        memset(o, 0, sizeof *o);
+        o->origin.x = r.o.x; o->origin.y = r.o.y; o->origin.z = r.o.z;
+        o->direction.x = r.d.x; o->direction.y = r.d.y; o->direction.z = r.d.z;
+        o->t_max = HG_INF;
+    }
 }
 
 /* ------------------------------------------------------------------------------------------------

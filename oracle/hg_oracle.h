@@ -62,6 +62,14 @@ int hgo_render(const hgo_scene* scene, const hg_params* params, int32_t n_frames
 void hgo_trace_pixel(const hgo_scene* scene, const hg_params* params, uint32_t x, uint32_t y, int32_t frame,
                      float rgb[3], hg_counters* counters);
 
+/* Ray queries (include/halogen_abi.h "Ray queries over the uploaded scene"), sequential.  hgo_intersect_batch: the
+ * oracle's get_ray_intersection for n caller rays, the closest distance seeded with t_max, no far plane, every sphere
+ * and mesh of the scene; hits[i] has hg_ray_hit's field meanings (a miss: kind HG_HIT_NONE, t = +inf, all else 0).
+ * hgo_camera_rays: the first camera ray (sample 0) frame `frame_count` traces for each listed pixel (x0, y0, x1, ...),
+ * t_max = +inf: get_ray seeded as the render seeds it. */
+void hgo_intersect_batch(const hgo_scene* scene, const hg_ray* rays, hg_ray_hit* hits, int64_t n);
+void hgo_camera_rays(const hg_params* params, int32_t frame_count, const int32_t* pixels_xy, hg_ray* rays, int64_t n);
+
 /* Diagnostics, collected only by the stats build (HGO_STATS=1: build/libhgoracle_stats.so; the plain build keeps
  * the traversal free of them and reports zeros, max_depth -1).  hgo_stats_build() says which build this is.
  * Mesh traversals (since the last reset) whose node stack would hold more than the reference's NodeStack[32]

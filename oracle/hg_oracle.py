@@ -85,6 +85,10 @@ def lib(stats: bool = False):
         L.hgo_cube_adjacent.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
         L.hgo_stats_build.restype = C.c_int
         L.hgo_stats_build.argtypes = []
+        L.hgo_intersect_batch.restype = None
+        L.hgo_intersect_batch.argtypes = [C.POINTER(HgoScene), C.c_void_p, C.c_void_p, C.c_int64]
+        L.hgo_camera_rays.restype = None
+        L.hgo_camera_rays.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]
         _libs[path] = L
     return _libs[path]
 
@@ -153,6 +157,30 @@ def visit_stats(reset: bool = False) -> dict:
     out = (C.c_uint64 * 6)()
     lib(True).hgo_visit_stats(out, 1 if reset else 0)
     return {"root": [int(x) for x in out[:3]], "inner": [int(x) for x in out[3:]]}
+
+
+def intersect_batch(packed, rays: np.ndarray) -> np.ndarray:
+    """The oracle's get_ray_intersection for caller rays (hgo_intersect_batch): rays as an (n, 8) float32 array or a
+    halogen.abi.RAY_DTYPE array (32 bytes per ray), hits as a halogen.abi.RAY_HIT_DTYPE array."""
+    from halogen import abi
+    a = np.ascontiguousarray(rays)
+    n = a.nbytes // 32
+    assert a.nbytes == 32 * n and a.dtype in (np.dtype(np.float32), abi.RAY_DTYPE)
+    hits = np.zeros(n, dtype=abi.RAY_HIT_DTYPE)
+    scene, keep = make_scene(packed)
+    lib().hgo_intersect_batch(C.byref(scene), a.ctypes.data, hits.ctypes.data, n)
+    del keep
+    return hits
+
+
+def camera_rays(params, frame_count: int, pixels) -> np.ndarray:
+    """The first camera ray frame `frame_count` traces for each (x, y) of `pixels`, as a halogen.abi.RAY_DTYPE array
+    with t_max = +inf (hgo_camera_rays)."""
+    from halogen import abi
+    px = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
+    rays = np.zeros(len(px), dtype=abi.RAY_DTYPE)
+    lib().hgo_camera_rays(C.byref(params), int(frame_count), px.ctypes.data, rays.ctypes.data, len(px))
+    return rays
 
 
 def cube_adjacent(face: int, i: int, j: int, size: int) -> tuple[int, int, int]:

@@ -3,7 +3,8 @@
  *
  *   hg_oracle_asan render SCENE.hgscene PARAMS.bin FRAMES THREADS OUT.f32 [CUBE.hgcube]
  *       the reference-layout scene (halogen/host_files.py write_scene), the raw hg_params block, FRAMES progressive
- *       frames on THREADS pthreads; writes the RGBA32F image (compared bit for bit with the unsanitized oracle)
+ *       frames on THREADS pthreads; writes the RGBA32F image (compared bit for bit with the unsanitized oracle); then
+ *       every pixel's camera ray through the ray queries (hgo_camera_rays, hgo_intersect_batch)
  *   hg_oracle_asan blas N_TRIS SEED
  *       hgo_build_blas (BVHGenerator.cs restated) on a random soup of N_TRIS triangles, every triangle in one leaf
  */
@@ -86,6 +87,32 @@ static int render(int argc, char** argv) {
     fclose(out);
     printf("rendered %lldx%lld x%d frames: %llu rays, %llu triangle tests\n", (long long)W, (long long)H, frames,
            (unsigned long long)counters.rays, (unsigned long long)counters.tri_tests);
+    /* the ray queries: every pixel's camera ray of the first frame through hgo_intersect_batch, unbounded and with
+     * t_max cut to half the distance found (exact-size arrays, so an overrun of either is caught) */
+    const int64_t n_px = W * H;
+    int32_t* px = malloc((size_t)n_px * 2 * sizeof(int32_t));
+    hg_ray* rays = malloc((size_t)n_px * sizeof(hg_ray));
+    hg_ray_hit* hits = malloc((size_t)n_px * sizeof(hg_ray_hit));
+    for (int64_t i = 0; i < n_px; i++) {
+        px[2 * i] = (int32_t)(i % W);
+        px[2 * i + 1] = (int32_t)(i / W);
+    }
+    hgo_camera_rays(params, params->frameCount, px, rays, n_px);
+    hgo_intersect_batch(&sc, rays, hits, n_px);
+    int64_t n_hit = 0, n_cut = 0;
+    for (int64_t i = 0; i < n_px; i++) {
+        if (hits[i].kind != HG_HIT_NONE) {
+            n_hit++;
+            rays[i].t_max = hits[i].t * 0.5f;
+        }
+    }
+    hgo_intersect_batch(&sc, rays, hits, n_px);
+    for (int64_t i = 0; i < n_px; i++) n_cut += hits[i].kind != HG_HIT_NONE;
+    printf("queried %lld camera rays: %lld hit, %lld within half that distance\n", (long long)n_px, (long long)n_hit,
+           (long long)n_cut);
+    free(px);
+    free(rays);
+    free(hits);
     for (int k = 0; k < 5; k++) free(arr[k]);
     free(cube);
     free(acc);

@@ -376,6 +376,42 @@ def test_anchors(driver):
     assert (p[15]["block"], p[15]["grid"]) == (64, 32400)
 
 
+def test_deepest_stack_spill_columns(driver):
+    """stack_depth 64, the deepest tree hg_pack_geometry accepts (tests/tree_cases.py chain62 at 40 x 24: 15 tiles, and
+    the 1080p image).  What the traversal needs, not the plan's formula again: thread j of a launch pushes stack entry
+    d >= kLds to word (d - kLds) * spill_stride + j of the spill buffer (hg_device.h Stack / RowStack; j = blockIdx *
+    blockDim + threadIdx, hg_mega.hip), with kLds = 16 in the lockstep and regenerating kernels and 12 in the streaming
+    one and the server.  So the buffer must hold word (63 - kLds) * stride + threads - 1, and a column base j must stay
+    below the stride."""
+    exe, items = driver
+    small = dict(tiles=15, W=40, H=24, stack_depth=64)
+    cases = [
+        case(debug_mode=1, n_frames=1, **small),       # 0: lockstep, 4 workgroups of 256
+        case(kernel=K_MEGA, n_frames=2, **small),      # 1: lockstep by option
+        case(kernel=K_REGEN, n_frames=2, **small),     # 2: regenerating, 2 waves per tile
+        case(kernel=K_STREAM, n_frames=2, **small),    # 3: streaming (the queue form: at most that many waves)
+        case(n_frames=3, **small),                     # 4: auto = streaming for a deep BLAS
+        case(n_frames=1, **small),                     # 5: one frame per call, and the server's sizes
+        case(stack_depth=64),                          # 6: 1080p, 64 frames
+    ]
+    p = plans(exe, cases)
+    want = [  # threads of the launch at most, kLds of its kernel, stride, bytes (all by hand)
+        (4 * 256, 16, 1024, 1024 * 52 * 4), (4 * 256, 16, 1024, 1024 * 52 * 4),
+        (30 * 64, 16, 1920, 1920 * 52 * 4), (30 * 64, 12, 1920, 1920 * 52 * 4),
+        (45 * 64, 12, 2880, 2880 * 52 * 4), (15 * 64, 12, 960, 960 * 52 * 4),
+        (32400 * 64, 12, 2073600, 431308800),
+    ]
+    for k, (threads, lds, stride, size) in enumerate(want):
+        assert (p[k]["grid"] * p[k]["block"], p[k]["spill_stride"], p[k]["spill_bytes"]) == (threads, stride, size), k
+        assert threads - 1 < stride and ((63 - lds) * stride + threads - 1) * 4 + 4 <= size, k
+    assert [p[k]["kernel"] for k in (2, 3, 4)] == [K_REGEN, K_STREAM, K_STREAM] and p[0]["regen"] == p[1]["regen"] == 0
+    # the server: one persistent wave per tile here, its own buffer and stride (hg_render.hip server_start)
+    sv = p[5]
+    assert (sv["sv_grid"], sv["sv_spill_bytes"]) == (15, 15 * 64 * 52 * 4)
+    assert ((63 - STREAM_LDS_STACK) * sv["sv_grid"] * 64 + sv["sv_grid"] * 64 - 1) * 4 + 4 <= sv["sv_spill_bytes"]
+    assert (p[6]["sv_grid"], p[6]["sv_spill_bytes"]) == (5120, 5120 * 64 * 52 * 4)
+
+
 def test_refusal_and_grid_limit(driver):
     """More than 2^26 - 1 work units is refused as a status; below, the split keeps the grid within the limit."""
     exe, _ = driver
