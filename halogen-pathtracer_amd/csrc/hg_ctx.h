@@ -85,7 +85,7 @@ struct hg_ctx {
         // was still adding to: the counting sort's two passes then disagreed and wrote out of range.)
         DevBuf tile_cost;              // per local tile, wave-clock cost since this stream's last sort
         DevBuf tile_order;             // the cost order this stream's launches read
-        DevBuf order_scratch;          // hg_order_tiles: histogram and claims (zeroed at allocation, left zeroed)
+        DevBuf order_scratch;          // hg_order.hip: histogram and claims (zeroed at allocation, left zeroed)
         DevBuf queue;                  // kQueue launches: the 8 unit heads + exit count (zeroed at allocation; the
                                        // last wave of each launch zeroes them again)
         bool tile_cost_valid = false;  // tile_cost holds costs for this tiling
@@ -97,7 +97,7 @@ struct hg_ctx {
     int next_lane = 0;     // chunks of at most HG_QUEUE_MAX_FRAMES frames: every lane in turn
     int next_lane_big = 0;  // longer chunks: lanes [0, HG_TRACE_LANES_BIG) in turn
 
-    // The render server (hg_mega.hip kServer): launches of the reference's one frame per call
+    // The render server (hg_mega.hip kServer and hg_server.h): launches of the reference's one frame per call
     // (at most HG_QUEUE_MAX_FRAMES frames, accumulating, streaming kernel) post their frames to persistent trace waves
     // that outlive the call, instead of launching; each frame's blend runs on `stream` behind a gate on its completion
     // count.  Stopped (the waves drain what was posted and leave) by every entry point that changes what the waves

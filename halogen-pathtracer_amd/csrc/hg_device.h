@@ -1,5 +1,6 @@
 // hg_device.h — device-side building blocks of the Halogen hot path shared by the kernels of hg_mega.hip
-// (lockstep, regenerating and streaming megakernels, and the render server's persistent form of the streaming one).
+// (lockstep, regenerating and streaming megakernels, and the render server's persistent form of the streaming one;
+// their schedulers are hg_sched.h and hg_server.h), the frame blends of hg_blend.hip and the ray queries.
 //
 // Every function restates a piece of the reference (file:line in its comment) in the reference's
 // operation order, compiled with -ffp-contract=off and the shared arithmetic spec include/hg_fmath.h, so the
@@ -116,6 +117,32 @@ __device__ __forceinline__ uint64_t wave_clock() {
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
     return t;
 }
+// A word of uncached device memory read by a scalar load that bypasses the scalar cache (glc); p wave-uniform (a kernel
+// argument).  The blends read the context's lost word so (hg_server_gate: once a server frame was lost, every later
+// blend into the accumulator is skipped until a clear or a checkpoint load resets the word), one load per workgroup;
+// the render server's waves and its gate poll their control words so.  The runtime allocates those words uncached (no
+// L2 holds them either), and the polling of idle waves stays off the CU's vector-memory pipe, whose texture units
+// return data in order: a vector poll of a contended coherent word held up the loads of the busy waves beside it (with
+// the idle waves of a frame's end polling, a posted frame took several times its trace time).
+__device__ __forceinline__ uint32_t sload_u32(const uint32_t* p) {
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
+    return v;
+}
+__device__ __forceinline__ unsigned long long sv_sload(const unsigned long long* p) {
+    unsigned long long v;
+    asm volatile("s_load_dwordx2 %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
+    return v;
+}
+// The same for a 32-bit word whose address the compiler takes for divergent (lane 0's branch: a value read from LDS
+// counts as divergent), made wave-uniform.  readfirstlane returns int: each half through uint32_t, or a low half
+// >= 2^31 would sign-extend over the high one.
+__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
+    const uint64_t a = reinterpret_cast<uint64_t>(p);
+    const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a >> 32)));
+    const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a)));
+    return sload_u32(reinterpret_cast<const uint32_t*>((uint64_t(hi) << 32) | lo));
+}
 // 64-lane ballot of a bool straight from the compare mask (the HIP __ballot(int) materialises the predicate in a
 // VGPR and compares it again)
 __device__ __forceinline__ uint64_t wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
@@ -217,6 +244,15 @@ __device__ __forceinline__ float4 fc_load(const float4* p) {
 __device__ __forceinline__ size_t fc_index(const HgKernelParams& kp, uint32_t f, size_t slot) {
     return fc_slot_frame(slot, f, uint32_t(kp.n_frames));
 }
+// The accumulation blend of one frame's colour, acc*(1-w) + c*w with w = 1/FrameCount (AccumulationShader.shader:33),
+// and what a launch that does not accumulate stores instead.  Every blend of the library is this one: the lockstep
+// kernel's in place and the frame-order blends of hg_blend.hip, the same operations in the same order.
+__device__ __forceinline__ float4 blend_frame(float4 a, f3 c, float frame_count) {
+    const float w = rcp_exact(frame_count);
+    const float k = 1.0f - w;
+    return make_float4(a.x * k + c.x * w, a.y * k + c.y * w, a.z * k + c.z * w, a.w * k + 1.0f * w);
+}
+__device__ __forceinline__ float4 frame_alone(f3 c) { return make_float4(c.x, c.y, c.z, 1.0f); }
 
 // Triangle ti's Moller-Trumbore operands from its packed 36-B record (v0, e1, e2): a = (v0, e1.x), b = (e1.yz, e2.xy),
 // cz = e2.z, as two 4-B-aligned 16-B loads and one 4-B load.  (The three SoA streams of rounds 1-2 put a leaf's

@@ -65,7 +65,7 @@ struct HgKernelParams {
     int32_t n_spheres, n_meshes;
     int32_t first_frame, n_frames, accumulate;
     // frame-parallel split (regenerating kernel): frame_split waves share each tile, wave k tracing frames
-    // [k*n_frames/split, (k+1)*n_frames/split) into frame_color (fc_index); hg_blend_frames then applies the
+    // [k*n_frames/split, (k+1)*n_frames/split) into frame_color (fc_index); hg_blend_frames_* (hg_blend.hip) then applies the
     // accumulation blend in frame order.  frame_split == 1: the kernel blends into acc itself.
     int32_t frame_split;
     float4* __restrict__ frame_color;  // render server: a ring of sv_ring frames, frame k at [(k & (sv_ring-1)) * slots]
@@ -82,7 +82,7 @@ struct HgKernelParams {
     uint32_t* __restrict__ queue;
     uint32_t resident_waves;
     // streaming launches without the queue and without a frame split: each wave traces wave_units consecutive units
-    // of the cost order (1: one tile per wave), its lanes taking their items one after another (UnitItems)
+    // of the cost order (1: one tile per wave), its lanes taking their items one after another (UnitItems, hg_sched.h)
     uint32_t wave_units;
     // render server: the host words in pinned host memory (HG_SV_HOST_*; [0] the post word, frames posted | stop << 32)
     const unsigned long long* __restrict__ sv_post;

@@ -124,7 +124,7 @@ inline HgCallPlan hg_plan_call(const HgPlanIn& in) {
     P.split = split;
     int chunk_max = HG_REGEN_MAX_CHUNK;
     // The streaming kernel (always) and the regenerating kernel (item scheduling or a frame split) store every
-    // frame's colour and blend them into the accumulator in frame order afterwards (hg_blend_frames): such a launch
+    // frame's colour and blend them into the accumulator in frame order afterwards (hg_blend.hip hg_blend_frames_*): such a launch
     // is traced on a trace stream and blended on the context stream (the trace pipeline, hg_ctx.h).
     P.items_k = regen && (stream_k || HG_REGEN_ITEMS);
     P.pipelined = regen && (P.items_k || split > 1);
@@ -208,7 +208,7 @@ struct HgServerPlan {
     uint32_t slots, grid;  // persistent waves the GPU holds, and the launch's
     size_t per_frame, spill_bytes;
     uint32_t frames_cap;  // frames of one lifetime: tiles * frames < 2^31
-    uint32_t div_magic, div_shift;  // unit -> frame (hg_mega.hip sv_frame): a shift, or a multiply-high and a shift
+    uint32_t div_magic, div_shift;  // unit -> frame (hg_server.h sv_frame): a shift, or a multiply-high and a shift
 };
 
 // The render server's launch for `tiles` > 0 local tiles at `waves` persistent waves per SIMD

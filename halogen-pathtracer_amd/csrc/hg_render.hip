@@ -1,4 +1,4 @@
-// hg_render.hip — rendering: the host half of the render server (hg_ctx::Server; device side hg_mega.hip kServer), the
+// hg_render.hip — rendering: the host half of the render server (hg_ctx::Server; device side hg_mega.hip kServer, hg_server.h), the
 // trace pipeline (chunks traced on the trace streams, blended in frame order on the context stream), render_now, which
 // launches what the plan of hg_plan.h decides, and hg_render / hg_ctx_flush, which hold and release frames.  Stands in
 // for the DispatchCompute / Blit calls of Assets/Scripts/Render Features/HalogenRenderPass.cs (RP:237-508).
@@ -69,7 +69,7 @@ int server_stop(hg_ctx* c) {
     hg_ctx::Server& S = c->sv;
     if (!S.running) return HG_OK;
     // the stop word carries the frames the host asked for: frames posted ahead of the calls (server_speculate) and not
-    // yet claimed are abandoned (the waves' view drops to it, hg_mega.hip sv_view)
+    // yet claimed are abandoned (the waves' view drops to it, hg_server.h sv_view)
     __atomic_store_n(&S.host[HG_SV_HOST_POST], static_cast<unsigned long long>(S.committed) | HG_SV_STOP, __ATOMIC_SEQ_CST);
     const double t0 = host_seconds();
     sv_trace("stop: %u frames committed, %u posted", S.committed, S.posted);
@@ -136,8 +136,8 @@ void set_scene(HgKernelParams& kp, const hg_ctx* c, uint32_t descent_t) {
 
 namespace {
 
-// ---- the render server (hg_ctx::Server; device side hg_mega.hip kServer) ------------------------------------------
-// The server closes itself after HG_OPT_SERVER_IDLE_US with nothing posted (the close handshake, hg_mega.hip sv_close:
+// ---- the render server (hg_ctx::Server; device side hg_mega.hip kServer, hg_server.h) ------------------------------------------
+// The server closes itself after HG_OPT_SERVER_IDLE_US with nothing posted (the close handshake, hg_server.h sv_close:
 // no host clock is involved in whether a post is taken).  A frame's gate gives up after 30 s, or at once when every
 // wave of the server has left with the frame's count short: the frame is lost (reported, the accumulator invalid).
 constexpr uint64_t kGateTimeoutTicks = 30ull * 100000000ull;  // 100-MHz s_memrealtime
@@ -259,7 +259,7 @@ int server_start(hg_ctx* c, const HgKernelParams& kp_in, int32_t fc) {
         HG_HIP(c, hipStreamSynchronize(c->stream));
     int rc = ensure_uncached(c, S.ring, size_t(ring) * per_frame);
     if (!rc) rc = ensure_uncached(c, S.done, size_t(ring) * 128u);
-    if (!rc) rc = ensure_uncached(c, S.ctl, HG_SV_CTL_BYTES);  // (polled by scalar loads: hg_mega.hip sv_sload)
+    if (!rc) rc = ensure_uncached(c, S.ctl, HG_SV_CTL_BYTES);  // (polled by scalar loads: hg_device.h sv_sload)
     if (!rc && spill_bytes) rc = ensure(c, S.spill, spill_bytes);
     if (rc) return rc;
     // The counts and heads are zeroed on the context stream: after the last lifetime's gates and blends, and before
@@ -322,7 +322,7 @@ int server_start(hg_ctx* c, const HgKernelParams& kp_in, int32_t fc) {
     return HG_OK;
 }
 
-// Post frame k = S.posted to the server: the host's half of the close handshake (hg_mega.hip sv_close).  Raise the post
+// Post frame k = S.posted to the server: the host's half of the close handshake (hg_server.h sv_close).  Raise the post
 // word, then read the closing word.  Not raised: the post is taken (a wave that closes later reads the post word after
 // this store).  Raised: the post is taken only if the closing wave's read of the post word included it (the close
 // word); else HG_E_UNSUPPORTED, nothing posted: the caller restarts the server and posts there.  The ring slot must be

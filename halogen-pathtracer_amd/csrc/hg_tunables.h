@@ -53,7 +53,7 @@
 // at 1 during get_ray_intersection (C2 +1 %, C5 +2 %, tools/sweeps/sweep69.txt).
 #define HG_TRAVERSE_PRIO 1
 #ifndef HG_TILE_ORDER
-#define HG_TILE_ORDER 1  // regen / stream kernels: dispatch tiles in descending cost of the previous launch (hg_order_tiles)
+#define HG_TILE_ORDER 1  // regen / stream kernels: dispatch tiles in descending cost of the previous launch (hg_order.hip)
 #endif
 #ifndef HG_ORDER_MIN_FRAMES
 #define HG_ORDER_MIN_FRAMES 16  // hg_render re-sorts the tile order once at least this many frames of costs were recorded
@@ -137,7 +137,7 @@
 // wave reads copy blockIdx.x % HG_SV_MIRRORS: the polling of thousands of idle waves spread over as many lines), one
 // host-poll ticket per XCD (blockIdx.x % 8), the count of waves that left (read by the gates: a frame whose count is
 // short once every wave has left is lost), and the closing word (0 open, 1 closing: the one wave that won it runs the
-// close handshake, hg_mega.hip sv_close)
+// close handshake, hg_server.h sv_close)
 #define HG_SV_MIRRORS 16u
 #define HG_SV_MIRROR_WORD 288u
 #define HG_SV_TICKET_WORD (HG_SV_MIRROR_WORD + 32u * HG_SV_MIRRORS)
@@ -161,7 +161,7 @@
 #define HG_SV_WAVES 5  // the render server's persistent waves per SIMD (hg_render.hip server_start)
 #endif
 #ifndef HG_SV_TILE_RUN
-// The render server's XCD heads take runs of this many consecutive tiles (hg_mega.hip sv_pull): head h (the XCD whose
+// The render server's XCD heads take runs of this many consecutive tiles (hg_server.h sv_pull, hg_items.h hg_sv_run_place): head h (the XCD whose
 // waves pull it first) runs h, h + 8, ..., so a CU's waves pull neighbouring tiles and the heads still interleave
 // finely over the frame (one contiguous band per head lost 1-3 %: per-XCD balance).  C3, server forced, one box, two
 // rounds (tools/sweeps/sweep_r06_server_runs.txt), runs of 1 / 4 / 8 / 16: strict 3,169-3,176 / 3,183-3,194 /

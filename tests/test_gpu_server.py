@@ -1,4 +1,4 @@
-"""The render server (HG_OPT_SERVER, csrc/hg_mega.hip kServer), through the C-ABI.  The tests
+"""The render server (HG_OPT_SERVER, csrc/hg_mega.hip kServer, csrc/hg_server.h), through the C-ABI.  The tests
 force it on (HG_OPT_SERVER 2: every qualifying call) except the one for the automatic choice (1, the default).
 
 The reference dispatches HalogenCompute once per frame (RP:327, RP:406).  hg_render calls of few accumulating frames on

@@ -1,4 +1,4 @@
-"""Multi-tile streaming waves (HG_OPT_WAVE_UNITS, csrc/hg_mega.hip UnitItems): a wave of a streaming launch without
+"""Multi-tile streaming waves (HG_OPT_WAVE_UNITS, csrc/hg_sched.h UnitItems): a wave of a streaming launch without
 the queue traces k consecutive tiles of the cost order, its lanes taking the k tiles' (pixel, frame) items one after
 another.  Which wave traces an item changes nothing, so every image and counter must equal the one-tile-per-wave
 render, the goldens and the oracle, bit for bit."""

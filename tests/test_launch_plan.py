@@ -56,7 +56,7 @@ static void plan() {
                 S.grid, S.per_frame, S.spill_bytes, S.frames_cap, S.div_magic, S.div_shift);
 }
 
-// unit -> frame as hg_mega.hip sv_frame computes it
+// unit -> frame as hg_server.h sv_frame computes it
 static void divide() {
     unsigned tiles, n;
     if (std::scanf("%u %u", &tiles, &n) != 2) return;

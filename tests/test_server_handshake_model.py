@@ -1,6 +1,6 @@
 """The render server's close handshake and stop word as a model (CPU), checked over every interleaving.
 
-The code: hg_mega.hip sv_close / sv_view / sv_wait (device) and hg_render.hip server_post_frame / server_stop (host),
+The code: hg_server.h sv_close / sv_view / sv_wait (device) and hg_render.hip server_post_frame / server_stop (host),
 DESIGN.md section 4.7b.  Both sides store, then load, with sequentially consistent system-scope atomics, so the model
 interleaves whole steps in program order:
   host, posting frame k:  H1 post word := k + 1;  H2 read the closing word;  if raised: H3 read the close word and take
@@ -73,7 +73,7 @@ def test_no_close_means_the_post_is_taken_and_a_later_closer_sees_it():
 
 
 def view_after(mirror_writes, view0):
-    """A wave's view (hg_mega.hip sv_view): raised by larger mirror counts; once the stop flag is in the mirror, set
+    """A wave's view (hg_server.h sv_view): raised by larger mirror counts; once the stop flag is in the mirror, set
     to the stop word's count (which may be lower: frames posted ahead are abandoned)."""
     mirror, view = 0, view0
     for w in mirror_writes:
