@@ -185,12 +185,28 @@ struct MediumStack {
 struct Mat {
     float4 albedo, spec_metal, emis_rough, absorb_ior, prio_id_r2;
 };
-__device__ __forceinline__ Mat load_mat(const HgKernelParams& kp, uint32_t m) {
-    const float4* p = kp.materials + 5 * m;
-    return Mat{p[0], p[1], p[2], p[3], p[4]};
+extern __shared__ __attribute__((aligned(16))) uint32_t hg_lds_stack[];  // (the wave's dynamic LDS, see Stack below)
+// float4 k of material m.  kLds: from the wave's LDS copy of the table at word kp.mat_lds_word (mat_lds_fill;
+// hg_layout.h hg_wave_lds_plan decides where it lies and whether a launch has one), else from global memory.
+template <bool kLds = false>
+__device__ __forceinline__ float4 mat_f4(const HgKernelParams& kp, uint32_t m, uint32_t k) {
+    if constexpr (kLds) return reinterpret_cast<const float4*>(hg_lds_stack + kp.mat_lds_word)[m * HG_MAT_F4 + k];
+    else return kp.materials[HG_MAT_F4 * m + k];
 }
+// copy the material table into the wave's LDS (one wave per workgroup)
+__device__ __forceinline__ void mat_lds_fill(const HgKernelParams& kp, uint32_t lane) {
+    float4* mt = reinterpret_cast<float4*>(hg_lds_stack + kp.mat_lds_word);
+    const uint32_t nf4 = uint32_t(kp.n_materials) * HG_MAT_F4;
+    for (uint32_t i = lane; i < nf4; i += 64u) mt[i] = kp.materials[i];
+}
+template <bool kMatLds = false>
+__device__ __forceinline__ Mat load_mat(const HgKernelParams& kp, uint32_t m) {
+    return Mat{mat_f4<kMatLds>(kp, m, 0), mat_f4<kMatLds>(kp, m, 1), mat_f4<kMatLds>(kp, m, 2), mat_f4<kMatLds>(kp, m, 3),
+               mat_f4<kMatLds>(kp, m, 4)};
+}
+template <bool kMatLds = false>
 __device__ __forceinline__ int32_t mat_priority(const HgKernelParams& kp, uint32_t m) {
-    return __float_as_int(kp.materials[5 * m + 4].x);
+    return __float_as_int(mat_f4<kMatLds>(kp, m, 4).x);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1158,26 +1174,29 @@ struct Medium {
     f3 absorb;
     uint32_t id;
 };
+template <bool kMatLds = false>
 __device__ __forceinline__ Medium medium_of(const HgKernelParams& kp, uint32_t m) {
-    const float4 ai = kp.materials[5 * m + 3];
-    const float4 pr = kp.materials[5 * m + 4];
+    const float4 ai = mat_f4<kMatLds>(kp, m, 3);
+    const float4 pr = mat_f4<kMatLds>(kp, m, 4);
     return Medium{ai.w, xyz(ai), __float_as_uint(pr.y)};
 }
 __device__ __forceinline__ Medium empty_medium() { return Medium{1.0f, mk(0, 0, 0), 0xFFFFFFFFu}; }
+template <bool kMatLds = false>
 __device__ __forceinline__ Medium top_medium(const HgKernelParams& kp, const MediumStack& ms) {
-    return ms.sp > 0 ? medium_of(kp, ms.get(ms.sp - 1)) : empty_medium();
+    return ms.sp > 0 ? medium_of<kMatLds>(kp, ms.get(ms.sp - 1)) : empty_medium();
 }
+template <bool kMatLds = false>
 __device__ void medium_push(const HgKernelParams& kp, MediumStack& ms, uint32_t m) {  // :582-622
     if (ms.sp == 0) {
         ms.s = uint64_t(m);
         ms.sp = 1;
         return;
     }
-    const int32_t prio = mat_priority(kp, m);
+    const int32_t prio = mat_priority<kMatLds>(kp, m);
     int ins = ms.sp;
-    if (prio > mat_priority(kp, ms.get(ms.sp - 1))) {
+    if (prio > mat_priority<kMatLds>(kp, ms.get(ms.sp - 1))) {
         for (int i = ms.sp - 1; i >= 0; --i) {
-            if (prio < mat_priority(kp, ms.get(i))) {
+            if (prio < mat_priority<kMatLds>(kp, ms.get(i))) {
                 ins = i + 1;
                 break;
             }
@@ -1191,9 +1210,10 @@ __device__ void medium_push(const HgKernelParams& kp, MediumStack& ms, uint32_t 
     ms.s = low | (high << 8) | (uint64_t(m) << (8 * ins));
     ms.sp++;
 }
+template <bool kMatLds = false>
 __device__ void medium_pop(const HgKernelParams& kp, MediumStack& ms, uint32_t id) {  // :627-642
     for (int i = 0; i < ms.sp; ++i) {
-        if (medium_of(kp, ms.get(i)).id == id) {
+        if (medium_of<kMatLds>(kp, ms.get(i)).id == id) {
             const uint64_t low_mask = i == 0 ? 0ull : (~0ull >> (64 - 8 * i));
             const uint64_t low = ms.s & low_mask;
             const uint64_t high = (i + 1 < 8) ? ((ms.s >> (8 * (i + 1))) << (8 * i)) : 0ull;
@@ -1250,30 +1270,31 @@ __device__ f3 material_brdf(const HgKernelParams& kp, const Sampler& smp, Ray& r
 // evaluate_material_hit :743-817
 // bt_out: the bounceTypes[] slot this hit increments (0 diffuse, 1 glossy, 2 transmission; a false hit counts as
 // transmission, :806)
+template <bool kMatLds = false>
 __device__ f3 evaluate_hit(const HgKernelParams& kp, const Sampler& smp, MediumStack& ms, Ray& ray, const Hit& hit,
                            const Mat& mt, uint32_t& bt_out) {
-    const Medium internal = medium_of(kp, hit.mat);
+    const Medium internal = medium_of<kMatLds>(kp, hit.mat);
     const int32_t prio = __float_as_int(mt.prio_id_r2.x);
     Medium cur, hm;
     bool trueHit = true;
     if (prio >= 0) {
-        trueHit = ms.sp == 0 || prio <= mat_priority(kp, ms.get(ms.sp - 1));
+        trueHit = ms.sp == 0 || prio <= mat_priority<kMatLds>(kp, ms.get(ms.sp - 1));
         if (hit.orient == 1.0f) {
-            cur = top_medium(kp, ms);
+            cur = top_medium<kMatLds>(kp, ms);
             hm = internal;
-            medium_push(kp, ms, hit.mat);
+            medium_push<kMatLds>(kp, ms, hit.mat);
         } else {
-            cur = ms.sp == 0 ? internal : top_medium(kp, ms);
-            medium_pop(kp, ms, internal.id);
-            hm = top_medium(kp, ms);
+            cur = ms.sp == 0 ? internal : top_medium<kMatLds>(kp, ms);
+            medium_pop<kMatLds>(kp, ms, internal.id);
+            hm = top_medium<kMatLds>(kp, ms);
         }
     } else {
         if (hit.orient == 1.0f) {
-            cur = top_medium(kp, ms);
+            cur = top_medium<kMatLds>(kp, ms);
             hm = internal;
         } else {
             cur = internal;
-            hm = top_medium(kp, ms);
+            hm = top_medium<kMatLds>(kp, ms);
         }
     }
     f3 att;
@@ -1281,7 +1302,7 @@ __device__ f3 evaluate_hit(const HgKernelParams& kp, const Sampler& smp, MediumS
         uint32_t bt = 0;
         att = material_brdf(kp, smp, ray, hit, mt, cur, hm, bt);
         bt_out = bt;
-        if (hit.orient > 0.0f && bt != 2u) medium_pop(kp, ms, internal.id);
+        if (hit.orient > 0.0f && bt != 2u) medium_pop<kMatLds>(kp, ms, internal.id);
     } else {
         ray.o = hit.pos - hit.n * 0.0001f;
         att = mk(1, 1, 1);

@@ -93,15 +93,17 @@ struct HgKernelParams {
     // tiling
     int32_t tiles_x, rank, n_ranks, n_local_tiles;
     uint32_t stack_depth;  // LDS traversal stack entries per lane
-    uint32_t mesh_lds_word;  // the mesh records' LDS copy starts at this word (mesh_lds_bytes, hg_mega.hip)
+    uint32_t mesh_lds_word;  // the mesh records' LDS copy starts at this word (hg_wave_lds_plan below)
     uint32_t descent_t;    // relaxed while-while threshold (hg_device.h isect_meshes), 0 = classic while-while
     uint32_t stream_deep;  // streaming kernel: the deep-BLAS shading thresholds (HG_STREAM_TMIN_DEEP / _RESHADE_DEEP)
+    uint32_t mat_lds_word;  // the material table's LDS copy starts at this word (kMatLds launches; hg_wave_lds_plan)
     uint32_t* __restrict__ spill;  // per-lane traversal stack entries beyond the LDS part (rarely touched)
     uint32_t spill_stride;          // = threads of the launch grid
     // cubemap
     int32_t cube_size, cube_mips;
     uint32_t cube_mip_offset[HG_MAX_CUBE_MIPS];  // in float4 texels
     // scene
+    int32_t n_materials;  // records of `materials` (what a wave copies into its LDS)
     const float4* __restrict__ spheres;
     const HgDevMesh* __restrict__ meshes;
     const float4* __restrict__ materials;
@@ -118,3 +120,51 @@ struct HgKernelParams {
 
 #define HG_NONE 0xFFFFFFFFu
 #define HG_SPHERE_BIT 0x80000000u
+
+// ---- the dynamic LDS of a one-wave workgroup of the regenerating and streaming kernels (hg_mega.hip) ----------------
+// `rows` of 64 words come first: the lane's throughput (rows 0-2), path colour (3-5) and sample sum (6-8), then, in the
+// streaming kernel, a spare row and the leaf-share words, then the traversal stack's LDS entries.  Two read-only tables
+// that are the same for every wave may follow, each copied by the wave once at its start:
+//   mesh records   HG_MESH_LDS_F4 float4 per mesh, after the rows, when they fit the budget;
+//   materials      HG_MAT_F4 float4 per material.  At spp 1 the kernels only initialise the sample-sum rows, before
+//                  the copy (hg_mega.hip mat_lds_begin), and never read or write them again (the sum of one sample
+//                  is the sample: sample_mean and the `one_sample` branches), so a table of at most
+//                  HG_SUM_ROWS_BYTES lives there and the launch needs no more LDS than without it.  Otherwise it
+//                  goes behind the mesh records (behind the rows, when those stay in global memory) if the budget
+//                  still allows; else the kernels read it from global memory.
+// The rows are never shortened and the mesh records are placed first, so the material table never displaces either.
+// A budget of 0 keeps both tables in global memory.
+#define HG_MAT_F4 5  // float4 per material record
+#define HG_ROW_SUM 6u  // first of the three sample-sum rows, both kernels
+#define HG_SUM_ROWS_BYTES (3u * 64u * 4u)
+
+struct HgWaveLdsPlan {
+    uint32_t mesh_word, mat_word;  // first LDS word of each table (mat_word: only with mat_lds)
+    uint32_t bytes;                // dynamic LDS bytes of the launch
+    bool mesh_lds, mat_lds;        // which tables the waves copy into LDS
+    bool mat_in_sum_rows;          // the material table lies in the sample-sum rows
+};
+
+inline HgWaveLdsPlan hg_wave_lds_plan(size_t rows_bytes, int32_t n_meshes, int32_t n_materials, uint32_t spp,
+                                      size_t budget) {
+    HgWaveLdsPlan p{uint32_t(rows_bytes / 4u), 0u, uint32_t(rows_bytes), false, false, false};
+    if (budget == 0) return p;
+    size_t end = rows_bytes;
+    const size_t mesh_bytes = n_meshes > 0 ? size_t(n_meshes) * HG_MESH_LDS_F4 * 16u : 0;
+    if (mesh_bytes && end + mesh_bytes <= budget) {
+        p.mesh_lds = true;
+        end += mesh_bytes;
+    }
+    const size_t mat_bytes = n_materials > 0 ? size_t(n_materials) * HG_MAT_F4 * 16u : 0;
+    if (mat_bytes && spp == 1u && mat_bytes <= HG_SUM_ROWS_BYTES &&
+        rows_bytes >= size_t(HG_ROW_SUM) * 256u + HG_SUM_ROWS_BYTES) {
+        p.mat_lds = p.mat_in_sum_rows = true;
+        p.mat_word = HG_ROW_SUM * 64u;
+    } else if (mat_bytes && end + mat_bytes <= budget) {
+        p.mat_lds = true;
+        p.mat_word = uint32_t(end / 4u);
+        end += mat_bytes;
+    }
+    p.bytes = uint32_t(end);
+    return p;
+}

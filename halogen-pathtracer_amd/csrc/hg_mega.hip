@@ -101,7 +101,7 @@ constexpr uint32_t kRegenLdsState = 9;  // words per lane: throughput, radiance,
 constexpr uint32_t kStreamLdsState = 10;
 // Streaming kernel LDS rows (one wave per workgroup, RowVec / RowStack): throughput 0-2, path colour 3-5, sample sum
 // 6-8, the distributed leaf test 10-12, the traversal stack from row 13.
-constexpr uint32_t kRowThr = 0, kRowCol = 3, kRowSum = 6, kRowLeaf = kStreamLdsState;
+constexpr uint32_t kRowThr = 0, kRowCol = 3, kRowSum = HG_ROW_SUM, kRowLeaf = kStreamLdsState;
 constexpr uint32_t kRowStack = kRowLeaf + kLeafShareWords;
 constexpr uint32_t kRegenRowStack = kRegenLdsState;  // regenerating kernel: rows 0-8 as above, the stack from row 9
 
@@ -112,7 +112,21 @@ __device__ __forceinline__ f3 sample_mean(const HgKernelParams& kp, f3 sum) {
     return mk(sum.x / sppf, sum.y / sppf, sum.z / sppf);
 }
 
-template <bool kCounters, bool kMeshLds>
+// The wave's copy of the material table (mat_f4, hg_device.h), made once the lanes' rows are initialised: at spp 1 the
+// table may lie in the sample-sum rows (hg_layout.h hg_wave_lds_plan), which no lane writes or reads after that
+// initialisation (sample_mean above and the one_sample branches of the shading loops: the sum of one sample is the
+// sample).  The render server's waves copy once per lifetime: every upload, a partial one included, stops the server
+// before it replaces a buffer (hg_upload_scene_gen's quiesce, hg_runtime.hip), as the mesh copy already relies on.
+template <bool kMatLds>
+__device__ __forceinline__ void mat_lds_begin(const HgKernelParams& kp, uint32_t lane) {
+    if constexpr (kMatLds) {
+        wave_lds_sync();
+        mat_lds_fill(kp, lane);
+        wave_lds_sync();
+    }
+}
+
+template <bool kCounters, bool kMeshLds, bool kMatLds>
 __global__ __launch_bounds__(HG_STREAM_LB, HG_MEGA_WAVES) void hg_trace_regen_kernel(const HgKernelParams kp) {
     const uint32_t lane = threadIdx.x & 63u;
     if (kMeshLds) {  // the wave's copy of the mesh records (mesh_f4, hg_device.h)
@@ -172,6 +186,7 @@ __global__ __launch_bounds__(HG_STREAM_LB, HG_MEGA_WAVES) void hg_trace_regen_ke
         s_col.set(mk(0, 0, 0));
         s_sum.set(mk(0, 0, 0));
     }
+    mat_lds_begin<kMatLds>(kp, lane);
     uint64_t cyc_trav = 0, cyc_shade = 0;  // wave clock (s_memtime) per phase, counting instantiation only
     while (__any(work)) {
         const uint64_t t0 = kCounters ? wave_clock() : 0;
@@ -187,10 +202,10 @@ __global__ __launch_bounds__(HG_STREAM_LB, HG_MEGA_WAVES) void hg_trace_regen_ke
             f3 thr = s_thr.get(), col = s_col.get();
             if (hit.t < kp.far_) {  // :898-936
                 c.hits++;
-                const Mat mt = load_mat(kp, hit.mat);
+                const Mat mt = load_mat<kMatLds>(kp, hit.mat);
                 col = col + xyz(mt.emis_rough) * thr;
                 uint32_t bt = 0;
-                const f3 att = evaluate_hit(kp, smp, ms, ray, hit, mt, bt);
+                const f3 att = evaluate_hit<kMatLds>(kp, smp, ms, ray, hit, mt, bt);
                 bounce += 1u << (8u * bt);
                 thr = thr * att;
                 acc_rough += mt.emis_rough.w * thr.x;
@@ -295,13 +310,6 @@ static void with_flags(F&& f, bool b, Rest... rest) {
     else with_flags([&](auto... k) { f(std::false_type{}, k...); }, rest...);
 }
 
-// LDS bytes with the mesh records after `base` bytes of rows, or 0 when they do not fit `budget` (or HG_MESH_LDS is off)
-static size_t mesh_lds_bytes(size_t base, int32_t n_meshes, size_t budget) {
-    if (n_meshes <= 0) return 0;
-    const size_t b = base + size_t(n_meshes) * HG_MESH_LDS_F4 * 16u;
-    return b <= budget ? b : 0;
-}
-
 hipError_t hg_launch_mega_regen(const HgKernelParams& kp_in, int block, bool counters, hipStream_t stream) {
     (void)block;  // one wave per workgroup (the kernel's LDS rows assume it)
     block = 64;
@@ -310,15 +318,17 @@ hipError_t hg_launch_mega_regen(const HgKernelParams& kp_in, int block, bool cou
     const uint32_t lds_depth = kp_in.stack_depth < HG_MEGA_LDS_STACK ? kp_in.stack_depth : HG_MEGA_LDS_STACK;
     const size_t lds = size_t(kRegenRowStack + lds_depth) * 64u * sizeof(uint32_t);
     HgKernelParams kp = kp_in;
-    kp.mesh_lds_word = uint32_t(lds / 4u);
-    const size_t mesh_lds = mesh_lds_bytes(lds, kp.n_meshes, HG_REGEN_LDS_BUDGET);
+    // which of the mesh records and the material table the waves keep in LDS, and where (hg_layout.h)
+    const HgWaveLdsPlan lp = hg_wave_lds_plan(lds, kp.n_meshes, HG_MAT_LDS_REGEN ? kp.n_materials : 0, kp.spp, HG_REGEN_LDS_BUDGET);
+    kp.mesh_lds_word = lp.mesh_word;
+    kp.mat_lds_word = lp.mat_word;
     const dim3 g{uint32_t(grid)}, b{uint32_t(block)};
     with_flags(
-        [&](auto C, auto M) {
-            hipLaunchKernelGGL((hg_trace_regen_kernel<decltype(C)::value, decltype(M)::value>), g, b,
-                               mesh_lds ? mesh_lds : lds, stream, kp);
+        [&](auto C, auto M, auto T) {
+            hipLaunchKernelGGL((hg_trace_regen_kernel<decltype(C)::value, decltype(M)::value, decltype(T)::value>), g, b,
+                               lp.bytes, stream, kp);
         },
-        counters, mesh_lds != 0);
+        counters, lp.mesh_lds, lp.mat_lds);
     return hipGetLastError();
 }
 
@@ -330,7 +340,7 @@ hipError_t hg_launch_mega_regen(const HgKernelParams& kp_in, int block, bool cou
 // Every frame's colour goes to frame_color (item scheduling), blended in frame order by hg_blend_frames.  kQueue: the
 // persistent work-queue form above (launches of few frames).
 // kServer (with kQueue): the render server's persistent form above.
-template <bool kCounters, bool kMeshLds, bool kQueue, bool kDeep, bool kServer>
+template <bool kCounters, bool kMeshLds, bool kMatLds, bool kQueue, bool kDeep, bool kServer>
 __global__ __launch_bounds__(HG_STREAM_LB, HG_STREAM_WAVES) void hg_trace_stream_kernel(const HgKernelParams kp) {
     static_assert(!kServer || kQueue, "the render server is a queue launch");
     // shade once at most kTmin lanes still traverse; reshade while at least kReshade need it (compile-time: as kernel
@@ -410,6 +420,7 @@ __global__ __launch_bounds__(HG_STREAM_LB, HG_STREAM_WAVES) void hg_trace_stream
             trav_begin<kMeshLds>(kp, ray, tv, c);
         }
     }
+    mat_lds_begin<kMatLds>(kp, lane);
     uint64_t cyc_trav = 0, cyc_shade = 0;  // wave clock (s_memtime) per phase, counting instantiation only
     __builtin_amdgcn_s_setprio(HG_TRAVERSE_PRIO);  // traversal waits on memory: its waves issue first
     for (;;) {  // (kServer: once per stretch of posted work; the others: once)
@@ -482,10 +493,10 @@ __global__ __launch_bounds__(HG_STREAM_LB, HG_STREAM_WAVES) void hg_trace_stream
                 const Hit hit = trav_hit<kMeshLds>(kp, ray, tv);
                 if (hit.t < kp.far_) {  // :898-936
                     c.hits++;
-                    const Mat mt = load_mat(kp, hit.mat);
+                    const Mat mt = load_mat<kMatLds>(kp, hit.mat);
                     col = col + xyz(mt.emis_rough) * thr;
                     uint32_t bt = 0;
-                    const f3 att = evaluate_hit(kp, smp, ms, ray, hit, mt, bt);
+                    const f3 att = evaluate_hit<kMatLds>(kp, smp, ms, ray, hit, mt, bt);
                     bounce += 1u << (8u * bt);
                     thr = thr * att;
                     acc_rough += mt.emis_rough.w * thr.x;
@@ -633,29 +644,32 @@ hipError_t hg_launch_mega_stream(const HgKernelParams& kp_in, int block, bool co
     const uint32_t lds_depth = kp_in.stack_depth < HG_STREAM_LDS_STACK ? kp_in.stack_depth : HG_STREAM_LDS_STACK;
     const size_t lds = size_t(kRowStack + lds_depth) * 64u * sizeof(uint32_t);
     HgKernelParams kp = kp_in;
-    kp.mesh_lds_word = uint32_t(lds / 4u);
-    const size_t mesh_lds = mesh_lds_bytes(lds, kp.n_meshes, HG_WAVE_LDS_BUDGET);
+    // which of the mesh records and the material table the waves keep in LDS, and where (hg_layout.h)
+    const HgWaveLdsPlan lp = hg_wave_lds_plan(lds, kp.n_meshes, HG_MAT_LDS_STREAM ? kp.n_materials : 0, kp.spp, HG_WAVE_LDS_BUDGET);
+    kp.mesh_lds_word = lp.mesh_word;
+    kp.mat_lds_word = lp.mat_word;
     const dim3 g{uint32_t(grid)}, b{64u};
-    const size_t sh = mesh_lds ? mesh_lds : lds;
+    const size_t sh = lp.bytes;
     // the last wave of the previous launch zeroed the heads and the exit count
     if (HG_CHECK_EXEC && queue && !server && kp.counters)
         hg_launch_check_zeroed(static_cast<const uint32_t*>(kp.queue), uint32_t(HG_QUEUE_BYTES / 4u), kp.counters + 18, stream);
     // D: deep BLAS (kp.stream_deep), the kDeep thresholds.  The server is a queue launch.
     if (server)
         with_flags(
-            [&](auto C, auto M, auto D) {
-                hipLaunchKernelGGL((hg_trace_stream_kernel<decltype(C)::value, decltype(M)::value, true, decltype(D)::value, true>),
+            [&](auto C, auto M, auto T, auto D) {
+                hipLaunchKernelGGL((hg_trace_stream_kernel<decltype(C)::value, decltype(M)::value, decltype(T)::value, true,
+                                                           decltype(D)::value, true>),
                                    g, b, sh, stream, kp);
             },
-            counters, mesh_lds != 0, kp.stream_deep != 0);
+            counters, lp.mesh_lds, lp.mat_lds, kp.stream_deep != 0);
     else
         with_flags(
-            [&](auto C, auto M, auto Q, auto D) {
-                hipLaunchKernelGGL((hg_trace_stream_kernel<decltype(C)::value, decltype(M)::value, decltype(Q)::value,
-                                                           decltype(D)::value, false>),
+            [&](auto C, auto M, auto T, auto Q, auto D) {
+                hipLaunchKernelGGL((hg_trace_stream_kernel<decltype(C)::value, decltype(M)::value, decltype(T)::value,
+                                                           decltype(Q)::value, decltype(D)::value, false>),
                                    g, b, sh, stream, kp);
             },
-            counters, mesh_lds != 0, queue, kp.stream_deep != 0);
+            counters, lp.mesh_lds, lp.mat_lds, queue, kp.stream_deep != 0);
     return hipGetLastError();
 }
 

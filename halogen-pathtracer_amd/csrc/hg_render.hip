@@ -128,6 +128,7 @@ void set_scene(HgKernelParams& kp, const hg_ctx* c, uint32_t descent_t) {
     kp.spheres = static_cast<const float4*>(c->spheres.p);
     kp.meshes = static_cast<const HgDevMesh*>(c->meshes.p);
     kp.materials = static_cast<const float4*>(c->materials.p);
+    kp.n_materials = c->n_materials;
     kp.nodes = static_cast<const float4*>(c->nodes.p);
     kp.leaves = static_cast<const uint2*>(c->leaves.p);
     kp.tris = static_cast<const float*>(c->tris.p);

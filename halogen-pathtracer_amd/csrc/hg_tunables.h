@@ -58,9 +58,16 @@
 #ifndef HG_ORDER_MIN_FRAMES
 #define HG_ORDER_MIN_FRAMES 16  // hg_render re-sorts the tile order once at least this many frames of costs were recorded
 #endif                          // since the last sort (64-frame launches: every launch; 1-frame launches: every 16th)
-// Every mesh's world->local matrix and header (80 B) in the wave's LDS when they fit (mesh_lds_bytes): the per-lane
+// Every mesh's world->local matrix and header (80 B) in the wave's LDS when they fit (hg_wave_lds_plan): the per-lane
 // mesh switch reads LDS, not global memory
 #define HG_MESH_LDS_F4 5  // float4 per cached mesh record: w2l columns 0-3, header (root, tri offset, material, cull)
+// The material table in the wave's LDS too (hg_layout.h hg_wave_lds_plan; 0: that kernel reads it from global memory)
+#ifndef HG_MAT_LDS_STREAM
+#define HG_MAT_LDS_STREAM 1
+#endif
+#ifndef HG_MAT_LDS_REGEN
+#define HG_MAT_LDS_REGEN 1
+#endif
 // Bytes of LDS per one-wave workgroup that still keep 20 waves (5 per SIMD) on a CU.  Measured, not derived from
 // 160 KiB / 20: 7,424 and 7,472 B run at full occupancy, 7,936 / 7,984 / 8,192 B lose 8-12 % (one wave fewer per
 // CU; tools/sweep_r02_h.txt); 7,680 is the largest multiple of 512 below the first failing size.
