@@ -207,6 +207,17 @@ public static class HalogenNative
         int nTriangles, ulong geometryGeneration);
     [DllImport(Lib)] public static extern int hg_scene_readback(IntPtr ctx, int which, [Out] byte[] dst,
         UIntPtr capacity, out UIntPtr nBytes);
+    // A rebuild gives one mesh a new tree on the device, in place (a linear BVH over the moved triangles, leaves of
+    // leafSize; 0: the smallest of 4..15 that fits the tree's records).  The mesh's triangle order becomes `order`
+    // (order[k]: the caller's index of the triangle now at k).  hg_build_blas_lbvh is the host twin: the same order, the
+    // triangles in it and the tree in the reference's format (2K - 1 entries), which the next full upload needs.
+    [DllImport(Lib)] public static extern long hg_build_blas_lbvh(HalogenTriangle[] triangles, int nTriangles,
+        int leafSize, [Out] int[] outOrder, [Out] HalogenTriangle[] outTriangles, [Out] BVHEntry[] outNodes,
+        long maxNodes);
+    [DllImport(Lib)] public static extern int hg_rebuild_mesh(IntPtr ctx, int meshIndex, HalogenTriangle[] triangles,
+        int nTriangles, int leafSize, [Out] int[] order, ulong geometryGeneration);
+    [DllImport(Lib)] public static extern int hg_rebuild_mesh_device(IntPtr ctx, int meshIndex, IntPtr dTriangles,
+        int nTriangles, int leafSize, IntPtr dOrder, ulong geometryGeneration);
 
     // Multi-GPU gather (one context per GPU; the render pass keeps one HalogenRenderPass per device and gathers the
     // tiles to the display device once per displayed image).

@@ -398,6 +398,30 @@ public class HalogenRenderPass : ScriptableRenderPass
         ClearAccumulation();
     }
 
+    // A deformed mesh whose refitted tree no longer fits the pose: a new tree, built on every device in place
+    // (hg_rebuild_mesh; not in the reference, which rebuilds with BVHGenerator on the host).  `moved`: the mesh's
+    // triangles in their current order; leafSize 1..15.  Returns the host twin's arrays (hg_build_blas_lbvh): the new
+    // order, the triangles in it and the tree (2K - 1 entries), which the component must hand out from now on, padded
+    // to its old entry count so that the buffer offsets, and with them the vouched re-upload, stay.  The image starts over.
+    internal (int[] order, HalogenTriangle[] triangles, BVHEntry[] nodes) RebuildMesh(int meshIndex,
+        HalogenTriangle[] moved, int leafSize)
+    {
+        if (leafSize < 1 || leafSize > 15)
+            throw new ArgumentOutOfRangeException(nameof(leafSize), "RebuildMesh: leafSize must be 1..15");
+        if (moved.Length == 0) throw new ArgumentException("RebuildMesh: no triangles");
+        int n = moved.Length, leaves = (n + leafSize - 1) / leafSize;
+        var order = new int[n];
+        var sorted = new HalogenTriangle[n];
+        var nodes = new BVHEntry[2 * leaves - 1];
+        long rc = HalogenNative.hg_build_blas_lbvh(moved, n, leafSize, order, sorted, nodes, nodes.Length);
+        if (rc != nodes.Length) throw new Exception($"hg_build_blas_lbvh failed ({rc})");
+        foreach (IntPtr ctx in contexts)
+            Check(HalogenNative.hg_rebuild_mesh(ctx, meshIndex, moved, n, leafSize, null, geometryGeneration),
+                  "hg_rebuild_mesh");
+        ClearAccumulation();
+        return (order, sorted, nodes);
+    }
+
     // Index of `material` in the packed list, packing it on first use (PackMaterialToList, RP:524-537: equality by
     // value, so identical materials share one slot).
     uint MaterialSlot(HalogenMaterial material)

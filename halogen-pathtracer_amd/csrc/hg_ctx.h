@@ -51,6 +51,19 @@ struct hg_ctx {
     std::map<uint64_t, RefitTree> refit_trees;
     DevBuf refit_in, refit_raw;  // the host-pointer form's triangles; one raw box (6 floats) per record of a tree
     uint64_t scene_refits = 0;
+    // Rebuild (hg_rebuild_mesh, hg_lbvh.hip).  Per rebuilt tree, by its triangle offset (the root ref changes with the
+    // tree): the first record and the record span of the tree at the last full upload, which is its capacity from then
+    // on (a rebuild may leave the tree with fewer records, or with none).  The build's device scratch, grown on demand.
+    struct RebuildSlot {
+        uint32_t rec_min = 0, capacity = 0;
+    };
+    std::map<uint32_t, RebuildSlot> rebuild_slots;
+    struct Lbvh {
+        DevBuf points, partial, bounds;       // key points (3 floats each); per-workgroup and final pmin / pmax
+        DevBuf codes, index, codes_sorted, index_sorted, sort_temp;
+        DevBuf tris, refs;                    // the triangles in the new order; the compact (refA, refB) per record
+    } lbvh;
+    uint64_t scene_rebuilds = 0;
 
     // cubemap
     DevBuf cube;

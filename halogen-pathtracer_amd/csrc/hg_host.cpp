@@ -9,6 +9,7 @@
 // depend on it), so the float arithmetic is kept in the reference's order: Unity's Bounds stores
 // centre/extents, so every min/max goes through  e=(max-min)*0.5, c=min+e, min=c-e, max=c+e.
 // Compiled with -ffp-contract=off.
+#include <algorithm>
 #include <atomic>
 #include <cfloat>
 #include <cmath>
@@ -25,6 +26,7 @@
 #include "halogen_abi.h"
 #include "hg_atrous.h"
 #include "hg_host_pool.h"
+#include "hg_lbvh.h"
 #include "hg_refit.h"
 
 namespace {
@@ -571,6 +573,66 @@ extern "C" int hg_refit_blas(const HalogenTriangle* tris, int32_t n_tris, BVHEnt
         nodes[g].boundingCornerB = {mx[0], mx[1], mx[2]};
     }
     return HG_OK;
+}
+
+// hg_build_blas_lbvh: the host twin of the device rebuild (hg_lbvh.hip), over the contract of hg_lbvh.h: key points,
+// grid, codes, the stable order, leaves of L, Karras' tree; then the boxes by hg_refit_blas.  Entry 0 is the root, the
+// children of internal node i are entries 1 + 2i and 2 + 2i.
+extern "C" int64_t hg_build_blas_lbvh(const HalogenTriangle* tris, int32_t n_tris, int32_t leaf_size, int32_t* out_order,
+                                      HalogenTriangle* out_tris, BVHEntry* out_nodes, int64_t max_nodes) {
+    if (!tris || !out_order || !out_tris || !out_nodes || n_tris < 1 || leaf_size < 1 ||
+        leaf_size > int32_t(HG_LBVH_MAX_LEAF) || uint32_t(n_tris) > HG_LBVH_MAX_TRIS)
+        return HG_E_INVALID;
+    const uint32_t n = uint32_t(n_tris), L = uint32_t(leaf_size), K = hg_lbvh_leaf_count(n, L);
+    const int64_t n_nodes = 2 * int64_t(K) - 1;
+    if (max_nodes < n_nodes) return -(n_nodes + 1);
+    const float inf = std::numeric_limits<float>::infinity();
+    float pmin[3] = {inf, inf, inf}, pmax[3] = {-inf, -inf, -inf};
+    std::vector<float> pts(size_t(n) * 3);
+    for (uint32_t t = 0; t < n; ++t) {
+        float* p = &pts[size_t(t) * 3];
+        hg_lbvh_key_point(tris[t], p);
+        for (int k = 0; k < 3; ++k) {
+            pmin[k] = hg_fminf(pmin[k], p[k]);
+            pmax[k] = hg_fmaxf(pmax[k], p[k]);
+        }
+    }
+    std::vector<uint32_t> code(n), sorted(n);
+    for (uint32_t t = 0; t < n; ++t) code[t] = hg_lbvh_code(&pts[size_t(t) * 3], pmin, pmax);
+    for (uint32_t t = 0; t < n; ++t) out_order[t] = int32_t(t);
+    std::stable_sort(out_order, out_order + n, [&](int32_t a, int32_t b) { return code[size_t(a)] < code[size_t(b)]; });
+    for (uint32_t k = 0; k < n; ++k) {
+        sorted[k] = code[size_t(out_order[k])];
+        out_tris[k] = tris[size_t(out_order[k])];
+    }
+    auto leaf_entry = [&](uint32_t j) {
+        uint32_t first, count;
+        hg_lbvh_leaf(n, L, j, first, count);
+        return BVHEntry{first, count, {0, 0, 0}, {0, 0, 0}};
+    };
+    auto inner_entry = [](uint32_t i) { return BVHEntry{1u + 2u * i, 0u, {0, 0, 0}, {0, 0, 0}}; };
+    out_nodes[0] = K == 1 ? leaf_entry(0) : inner_entry(0);
+    for (uint32_t i = 0; i + 1 < K; ++i) {
+        const HgLbvhNode nd = hg_lbvh_node(sorted.data(), L, int32_t(K), int32_t(i));
+        const uint32_t g = uint32_t(nd.split);
+        out_nodes[1 + 2 * size_t(i)] = nd.first == nd.split ? leaf_entry(g) : inner_entry(g);
+        out_nodes[2 + 2 * size_t(i)] = nd.last == nd.split + 1 ? leaf_entry(g + 1) : inner_entry(g + 1);
+    }
+    // the depth bound of hg_lbvh.h, asserted: a deeper tree would be a defect of the construction
+    uint32_t depth = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> walk{{0u, 0u}};
+    while (!walk.empty()) {
+        const auto [g, d] = walk.back();
+        walk.pop_back();
+        depth = std::max(depth, d);
+        if (d > HG_LBVH_MAX_DEPTH) break;  // (also ends a cycle, which a defect could make)
+        if (out_nodes[g].triangleCount) continue;
+        walk.push_back({out_nodes[g].indexA + 1, d + 1});
+        walk.push_back({out_nodes[g].indexA, d + 1});
+    }
+    if (depth > hg_lbvh_depth_bound(K)) return HG_E_UNSUPPORTED;
+    if (int rc = hg_refit_blas(out_tris, n_tris, out_nodes, int32_t(n_nodes))) return rc;
+    return n_nodes;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

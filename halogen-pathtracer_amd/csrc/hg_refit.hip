@@ -123,6 +123,10 @@ __global__ __launch_bounds__(kRefitBlock) void hg_refit_level(const uint32_t* __
     q[3] = make_float4(hi[0], hi[1], hi[2], 0.0f);
 }
 
+}  // namespace
+
+namespace hgrt {
+
 // Everything hg_refit_mesh* checks before the first device write.  On success: the tree (its plan built and cached on
 // first use) and the meshes refitted together (the instances of the tree: same root ref, same triangle offset).
 int refit_check(hg_ctx* c, int32_t mesh_index, const void* tris, int32_t n_tris, hg_ctx::RefitTree*& tree,
@@ -230,13 +234,10 @@ int refit_device(hg_ctx* c, hg_ctx::RefitTree& tree, const std::vector<int32_t>&
     return HG_OK;
 }
 
-}  // namespace
-
-namespace hgrt {
-
 void refit_reset(hg_ctx* c) {
     for (auto& kv : c->refit_trees) release(kv.second.list);
     c->refit_trees.clear();
+    c->rebuild_slots.clear();
 }
 
 }  // namespace hgrt

@@ -1,5 +1,5 @@
 // hg_rt.h — what the runtime's translation units (hg_runtime.hip, hg_render.hip, hg_display.hip, hg_query.hip,
-// hg_denoise.hip, hg_refit.hip, hg_comm.hip) share over a context: private to libhalogen_hip.so, none of it in the C-ABI.  The
+// hg_denoise.hip, hg_refit.hip, hg_lbvh.hip, hg_comm.hip) share over a context: private to libhalogen_hip.so, none of it in the C-ABI.  The
 // helpers are in namespace hgrt (each is defined in the file named beside it); the hg_ctx_* functions are the
 // context's services to hg_comm.hip and to each other.
 #pragma once
@@ -80,5 +80,12 @@ int query_params(hg_ctx* c, uint32_t threads, HgKernelParams& kp);
 // ---- hg_refit.hip ----
 // Forget the refit plans of the device scene and free their device lists (a full upload lays the records out anew)
 void refit_reset(hg_ctx* c);
+// Everything hg_refit_mesh* checks before the first device write.  On success: the tree (its plan built and cached on
+// first use; every other tree's plan is cached too) and the meshes refitted together.  Then the refit itself, from
+// n_tris HalogenTriangle on the device (4-byte aligned), for a context that is quiesced (hg_lbvh.hip runs both too)
+int refit_check(hg_ctx* c, int32_t mesh_index, const void* tris, int32_t n_tris, hg_ctx::RefitTree*& tree,
+                std::vector<int32_t>& instances);
+int refit_device(hg_ctx* c, hg_ctx::RefitTree& tree, const std::vector<int32_t>& instances, const void* d_tris,
+                 int32_t n_tris, uint64_t geometry_generation);
 
 }  // namespace hgrt

@@ -43,6 +43,9 @@ constexpr uint32_t kMaxStack = 64;  // LDS stack entries per lane; BLAS depth mu
 constexpr int kHostThreads = 16;    // host threads of hg_upload_scene's compare / repack (the GPU box's CPU share)
 static_assert(HG_REFIT_MAX_DEPTH == kMaxStack - 2, "hg_refit_blas accepts the depths hg_pack_geometry accepts");
 
+// The traversal stack entries per lane for a scene whose deepest BLAS entry is `max_depth` levels below its root
+inline uint32_t hg_stack_depth(uint32_t max_depth) { return std::max<uint32_t>(2u, (max_depth + 2 + 1) & ~1u); }
+
 struct HgPackError {
     int code = HG_OK;
     std::string text;
@@ -549,6 +552,6 @@ inline int hg_pack_geometry(const HgSceneIn& in, HgScenePack& out, HgPackError& 
         return hg_pack_fail(err, HG_E_UNSUPPORTED, "BLAS too large: %zu device node records", rec.size() / 4);
     if (rec.empty()) new_record();
     if (leaf.empty()) leaf.push_back(make_uint2(0, 0));
-    out.stack_depth = std::max<uint32_t>(2u, (max_depth + 2 + 1) & ~1u);
+    out.stack_depth = hg_stack_depth(max_depth);
     return HG_OK;
 }

@@ -160,6 +160,7 @@ EXPORTS = [
     "hg_comm_readback", "hg_comm_readback_begin", "hg_comm_readback_end", "hg_comm_set_timeout_ms", "hg_comm_transport", "hg_comm_last_error", "hg_comm_destroy",
     "hg_comm_assemble_host",
     "hg_refit_blas", "hg_refit_mesh", "hg_refit_mesh_device", "hg_scene_readback",
+    "hg_build_blas_lbvh", "hg_rebuild_mesh", "hg_rebuild_mesh_device",
 ]
 # hg_scene_readback: the device scene's arrays (layouts private to the library, csrc/hg_layout.h)
 HG_SCENE_NODES, HG_SCENE_LEAVES, HG_SCENE_TRIS, HG_SCENE_NORMALS, HG_SCENE_MESHES = 0, 1, 2, 3, 4
@@ -241,6 +242,9 @@ def lib() -> C.CDLL:
         "hg_refit_mesh": (C.c_int, [P, i32, P, i32, C.c_uint64]),
         "hg_refit_mesh_device": (C.c_int, [P, i32, P, i32, C.c_uint64]),
         "hg_scene_readback": (C.c_int, [P, i32, P, sz, C.POINTER(sz)]),
+        "hg_build_blas_lbvh": (i64, [P, i32, i32, P, P, P, i64]),
+        "hg_rebuild_mesh": (C.c_int, [P, i32, P, i32, i32, P, C.c_uint64]),
+        "hg_rebuild_mesh_device": (C.c_int, [P, i32, P, i32, i32, P, C.c_uint64]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -474,6 +478,37 @@ class Context:
             n, keep = len(triangles), triangles
         self._check(lib().hg_refit_mesh(self._h, int(mesh_index), _ptr(keep), n, int(generation)), "hg_refit_mesh")
 
+    def rebuild_mesh(self, mesh_index: int, triangles, leaf_size: int = 0, generation: int = 0):
+        """Give mesh `mesh_index` of the uploaded scene a new tree over its moved triangles, built on the device in place
+        (hg_rebuild_mesh, hg_rebuild_mesh_device): a linear BVH with leaves of `leaf_size` (0: the smallest of 4..15
+        whose records fit the tree's capacity).  triangles: as refit_mesh takes them, in the mesh's current order.
+        Returns the new order: order[k] is the index, in `triangles`, of the triangle now at position k; a torch int32
+        tensor on the device for a torch tensor, a numpy int32 array otherwise.  The mesh's triangles are in that order
+        from now on (later refit_mesh / rebuild_mesh calls, hg_ray_hit.primitive).  The accumulation is not cleared."""
+        if hasattr(triangles, "data_ptr") and not isinstance(triangles, np.ndarray):
+            import torch
+
+            if not (triangles.is_cuda and triangles.device.index == self.device and triangles.dtype == torch.float32 and
+                    triangles.dim() == 2 and triangles.shape[1] == 18 and triangles.is_contiguous()):
+                raise ValueError(f"device triangles must be a contiguous (n, 18) float32 tensor on cuda:{self.device}")
+            order = torch.empty(triangles.shape[0], dtype=torch.int32, device=triangles.device)
+            torch.cuda.current_stream(triangles.device).synchronize()  # the triangles are complete before the call
+            self._check(lib().hg_rebuild_mesh_device(self._h, int(mesh_index), C.c_void_p(triangles.data_ptr()),
+                                                     triangles.shape[0], int(leaf_size), C.c_void_p(order.data_ptr()),
+                                                     int(generation)), "hg_rebuild_mesh_device")
+            return order
+        if isinstance(triangles, np.ndarray):
+            a = np.ascontiguousarray(triangles)
+            if a.nbytes % C.sizeof(HalogenTriangle):
+                raise ValueError("triangles must hold 72 bytes per triangle")
+            n, keep = a.nbytes // C.sizeof(HalogenTriangle), a
+        else:
+            n, keep = len(triangles), triangles
+        order = np.zeros(n, dtype=np.int32)
+        self._check(lib().hg_rebuild_mesh(self._h, int(mesh_index), _ptr(keep), n, int(leaf_size), _ptr(order),
+                                          int(generation)), "hg_rebuild_mesh")
+        return order
+
     def scene_readback(self, which) -> np.ndarray:
         """A diagnostic copy of one array of the device scene ("nodes", "leaves", "tris", "normals", "meshes" or an
         HG_SCENE_* value) as bytes: two contexts hold the same scene exactly when all five are equal."""
@@ -646,6 +681,21 @@ def refit_blas(triangles, nodes) -> None:
     rc = lib().hg_refit_blas(_ptr(triangles), len(triangles), _ptr(nodes), len(nodes))
     if rc != HG_OK:
         raise HalogenError(f"hg_refit_blas failed ({rc}): a range, the depth or a cycle of the tree", rc)
+
+
+def build_blas_lbvh(triangles, leaf_size: int):
+    """hg_build_blas_lbvh, the host twin of Context.rebuild_mesh: one mesh's triangles (a ctypes array of
+    HalogenTriangle) -> (order, triangles in that order, nodes): a numpy int32 array and two ctypes arrays; the tree has
+    its root at entry 0 and mesh-relative indices, as hg_upload_scene takes it.  Needs no GPU."""
+    n = len(triangles)
+    leaves = (n + int(leaf_size) - 1) // int(leaf_size) if 1 <= int(leaf_size) <= 15 else 1
+    order = np.zeros(max(n, 1), dtype=np.int32)
+    out = (HalogenTriangle * max(n, 1))()
+    nodes = (BVHEntry * (2 * max(leaves, 1) - 1))()
+    rc = lib().hg_build_blas_lbvh(_ptr(triangles), n, int(leaf_size), _ptr(order), _ptr(out), _ptr(nodes), len(nodes))
+    if n == 0 or rc != len(nodes):
+        raise HalogenError(f"hg_build_blas_lbvh failed ({rc}): no triangles, or leaf_size outside 1..15", int(rc))
+    return order[:n], out, nodes
 
 
 def pack_display(rgba: np.ndarray, fmt: int) -> np.ndarray:

@@ -178,6 +178,7 @@ class HalogenRenderPass:
         # counts, in order) differ from the last upload's, so a camera move's re-upload compares only the small arrays
         self._geometry = (None, 0)
         self._deform_serials = []  # each mesh's deform_serial at the last upload (a change: refit, not rebuild)
+        self._rebuild_serials = []  # ... and its rebuild_serial (one more: a device rebuild, then a refit if it moved on)
         self.rank, self.n_ranks = 0, 1
         # display (RP:343-347): the reference's camera target is R11G11B10 float (URP-HighFidelity.asset:26-27)
         self.display_format = abi.HG_DISPLAY_R11G11B10F
@@ -221,15 +222,23 @@ class HalogenRenderPass:
         if hasattr(scene, "meshes") and hasattr(scene, "pack"):
             sig = tuple((m.cache_token, m.triangle_count, len(m.bvh)) for m in scene.meshes)
             serials = [m.deform_serial for m in scene.meshes]
-            if sig != self._geometry[0]:
+            rebuilds = [m.rebuild_serial for m in scene.meshes]
+            # a mesh rebuilt more than once since the last upload: the device's triangle order is no rebuild's input
+            # order any more, so the scene is uploaded in full (pack() is always current)
+            if sig != self._geometry[0] or any(r - r0 > 1 for r, r0 in zip(rebuilds, self._rebuild_serials)):
                 self._geometry = (sig, self._geometry[1] + 1)
             else:
-                # deformed meshes (RayTracingMesh.deform: same topology, moved vertices): their triangles and BVH boxes
-                # are refitted on the device under the current generation, so the upload below stays vouched
+                # deformed meshes (RayTracingMesh.deform: moved vertices): where asked (rebuild=True) the mesh's tree is
+                # rebuilt on the device from the rebuild's own input, otherwise the triangles and BVH boxes are refitted
+                # there; both under the current generation, so the upload below stays vouched
                 for i, m in enumerate(scene.meshes):
-                    if serials[i] != self._deform_serials[i]:
+                    if rebuilds[i] != self._rebuild_serials[i]:
+                        self.ctx.rebuild_mesh(i, m.rebuild_input, m.rebuild_leaf, self._geometry[1])
+                        if serials[i] != m.rebuild_at:
+                            self.ctx.refit_mesh(i, m.packed_triangles, self._geometry[1])
+                    elif serials[i] != self._deform_serials[i]:
                         self.ctx.refit_mesh(i, m.packed_triangles, self._geometry[1])
-            self._deform_serials = serials
+            self._deform_serials, self._rebuild_serials = serials, rebuilds
             generation = self._geometry[1]
         self.ctx.upload_scene(packed, generation)
         self._guides_dirty = True

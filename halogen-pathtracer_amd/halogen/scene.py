@@ -117,6 +117,9 @@ class RayTracingMesh:
         self.max_hierarchy_depth = int(max_hierarchy_depth)
         self.blas_builder = _blas_builder
         self.deform_serial = 0  # deform() calls since the geometry was cached
+        # deform(rebuild=True) calls, and of the last one: its input (the moved triangles in the order before it, which
+        # is the device's until the pass rebuilds), its leaf size, and deform_serial right after it
+        self.rebuild_serial, self.rebuild_input, self.rebuild_leaf, self.rebuild_at = 0, None, 0, 0
         self._cache()
 
     def _cache(self):
@@ -144,29 +147,58 @@ class RayTracingMesh:
             raise abi.HalogenError(f"hg_build_blas failed for {self.name}: {n}")
         self.bvh = (abi.BVHEntry * n)()
         C.memmove(self.bvh, nodes, n * C.sizeof(abi.BVHEntry))
+        # inner entries of the current tree: the records a device rebuild may certainly use (the device keeps the record
+        # span of the tree it was last given in full, which is never smaller than the current tree's)
+        self.bvh_inner = int((np.frombuffer(self.bvh, dtype=np.uint32).reshape(-1, 8)[:, 1] == 0).sum()) if n else 0
         self.packed_triangles = (abi.HalogenTriangle * n_tris)()
         rc = L.hg_pack_triangles(self.vertices.ctypes.data, self.normals.ctypes.data, len(self.vertices),
                                  self.triangles.ctypes.data, n_tris, C.cast(self.packed_triangles, C.c_void_p))
         if rc != 0:
             raise abi.HalogenError(f"hg_pack_triangles failed for {self.name}: {rc}")
 
-    def deform(self, vertices, normals=None) -> None:
+    def deform(self, vertices, normals=None, rebuild: bool = False, leaf_size: int = 0) -> None:
         """Move the vertices (same count; skinning, cloth, a morph target) and keep the topology: the triangles are
         repacked through the index list the BLAS build already permuted, and the BLAS is refitted on the host
         (hg_refit_blas: every box from the moved triangles, the tree as it was), so pack() is always current.  The
         cache token stays (the geometry generation does not change); deform_serial tells the pass to refit the device
         (Context.refit_mesh) instead of rebuilding.  A refitted tree is valid for any deformation and as tight as the
-        builder's boxes, but its split planes are the rest pose's: large deformations trace slower than a rebuild."""
+        builder's boxes, but its split planes are the rest pose's: large deformations trace slower than a rebuild.
+
+        rebuild=True gives the mesh a new tree over the moved triangles instead (abi.build_blas_lbvh, the host twin of
+        Context.rebuild_mesh: a linear BVH with leaves of leaf_size; 0: the smallest of 4..15 whose tree fits).  A tree
+        fits when it has no more inner entries than the mesh's current tree: that many records the device certainly
+        has for it, whether or not a full upload came in between, so the room never grows back after a rebuild with
+        larger leaves; a leaf size that does not fit raises ValueError before anything is changed.  The triangle order changes: the index list is permuted with it, so later plain deforms repack in
+        the new order.  The BVH array keeps its length (entries past the new tree are unreachable padding) and the cache
+        token stays, so the pass rebuilds on the device (rebuild_serial) and its next upload is still vouched."""
         v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         n = self.normals if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
         if v.shape != self.vertices.shape or n.shape != v.shape:
             raise ValueError("deform keeps the vertex count")
+        fit = []
+        if rebuild and len(self.triangles):
+            n_tris = len(self.triangles)
+            sizes = [int(leaf_size)] if leaf_size else range(4, 16)
+            fit = [k for k in sizes if 1 <= k <= 15 and (n_tris + k - 1) // k - 1 <= self.bvh_inner]
+            if not fit:
+                raise ValueError(f"{self.name}: no LBVH with leaf size {leaf_size or '4..15'} fits the {self.bvh_inner} "
+                                 f"inner entries of its tree")
         self.vertices, self.normals = v, n
         rc = abi.lib().hg_pack_triangles(v.ctypes.data, n.ctypes.data, len(v), self.triangles.ctypes.data,
                                          len(self.triangles), C.cast(self.packed_triangles, C.c_void_p))
         if rc != 0:
             raise abi.HalogenError(f"hg_pack_triangles failed for {self.name}: {rc}")
-        if len(self.triangles):
+        if fit:
+            moved = (abi.HalogenTriangle * n_tris)()
+            C.memmove(moved, self.packed_triangles, C.sizeof(moved))
+            order, self.packed_triangles, nodes = abi.build_blas_lbvh(moved, fit[0])
+            self.triangles = np.ascontiguousarray(self.triangles[order])
+            C.memset(self.bvh, 0, C.sizeof(self.bvh))
+            C.memmove(self.bvh, nodes, C.sizeof(nodes))
+            self.bvh_inner = (n_tris + fit[0] - 1) // fit[0] - 1
+            self.rebuild_serial += 1
+            self.rebuild_input, self.rebuild_leaf, self.rebuild_at = moved, fit[0], self.deform_serial + 1
+        elif len(self.triangles):
             abi.refit_blas(self.packed_triangles, self.bvh)
         self.deform_serial += 1
 

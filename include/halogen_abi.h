@@ -14,7 +14,8 @@
  *       blit (AccumulationShader.shader:27-34)
  *     - Dispose / Release                RP:410-423              -> hg_destroy
  *   plus what the reference never had: readback, counters, error text, multi-GPU tiling, ray queries, the denoised
- *   display, and deforming meshes (hg_refit_mesh: a device refit of one mesh's triangles and BVH boxes).
+ *   display, and deforming meshes (hg_refit_mesh: a device refit of one mesh's triangles and BVH boxes;
+ *   hg_rebuild_mesh: a new tree for one mesh, built on the device in place).
  *
  * The host structs below are byte-identical to the reference's C# blittable structs
  * (RP:10-76, strides from Marshal.SizeOf at RP:163-167): a C# caller passes its List<T>.ToArray()
@@ -363,6 +364,45 @@ int hg_refit_mesh(hg_ctx* ctx, int32_t mesh_index, const HalogenTriangle* triang
 int hg_refit_mesh_device(hg_ctx* ctx, int32_t mesh_index, const void* d_triangles, int32_t n_triangles,
                          uint64_t geometry_generation);
 int hg_scene_readback(hg_ctx* ctx, int32_t which, void* dst, size_t capacity, size_t* n_bytes);
+
+/* ----------------------------------------------------------------------------------------------
+ * A REBUILD gives one mesh of the uploaded scene a new tree, on the device and in place, when a refitted tree no longer
+ * fits the pose: "refit every frame, rebuild every N".  The tree is a linear BVH: the triangles in Morton order of
+ * their box centres (30-bit codes on the mesh's own grid), cut into leaves of `leaf_size`, under Karras' radix tree;
+ * csrc/hg_lbvh.h fixes every choice, so the host twin hg_build_blas_lbvh and the device build the same tree bit for bit.
+ * Its boxes are the refit's (csrc/hg_refit.h).  Not in the reference, which rebuilds with BVHGenerator on the host.
+ *
+ * hg_rebuild_mesh / hg_rebuild_mesh_device take the moved triangles of mesh `mesh_index` in the mesh's CURRENT order
+ * (n_triangles must be the tree's triangle extent), sort them, write them and their normals over the mesh's triangle
+ * range, write the new tree's records over the first records of the tree's own range, and refit: boxes, the cull boxes
+ * of every instance, the mesh table.  `order` / `d_order` (n_triangles int32, optional): order[k] is the caller's index
+ * of the triangle now at position k.  THE MESH'S TRIANGLE ORDER IS NOW `order`: hg_ray_hit.primitive and every later
+ * hg_refit_mesh* or hg_rebuild_mesh* call use it.  leaf_size 1..15 is taken as given; 0 picks the smallest L >= 4 whose
+ * K - 1 records (K = ceil(n / L) leaves) fit the tree's capacity.  The capacity is the span of the tree's records at the
+ * last full upload; it does not shrink after a rebuild, and growing the node array is out of scope.  A full upload lays
+ * the records out for the tree it is given, so after one the capacity is THAT tree's span: room given up by a rebuild
+ * with larger leaves does not come back, on the device or through an upload of the twin's arrays.
+ * Flush, quiesce, guide images, accumulation and tile cost order behave as a refit's do, and so does the upload rule
+ * afterwards (a vouched upload reads neither triangles nor entries; every other upload is a full upload, which needs the
+ * twin's arrays: hg_build_blas_lbvh's triangles and entries for this mesh).  The traversal stack depth becomes what a
+ * full upload of the scene with this tree would set.
+ * Refused, with text in hg_last_error and the device untouched: everything a refit refuses; n_triangles other than the
+ * tree's triangle extent or 0, a leaf_size outside 0..15, a device pointer that is not 4-byte aligned (HG_E_INVALID);
+ * K - 1 above the capacity, or no L <= 15 that fits; a triangle range that ends past 2^27, since a rebuilt tree's
+ * leaves are inline refs (HG_E_UNSUPPORTED).
+ *
+ * hg_build_blas_lbvh: the host twin.  One mesh's triangles in, `out_order`, `out_triangles` (the triangles in that
+ * order) and the tree in the reference's format out: root at entry 0, the children of internal node i at entries
+ * 1 + 2i and 2 + 2i, 2K - 1 entries, mesh-relative indices, boxes by hg_refit_blas.  Depth at most 30 + bits(K - 1) <= 58.
+ * hg_upload_scene accepts the result.  Returns the entry count, -(count + 1) if max_nodes is too small, or
+ * HG_E_INVALID (a null array, n_triangles < 1 or > 2^27, leaf_size outside 1..15).
+ * -------------------------------------------------------------------------------------------- */
+int64_t hg_build_blas_lbvh(const HalogenTriangle* triangles, int32_t n_triangles, int32_t leaf_size,
+                           int32_t* out_order, HalogenTriangle* out_triangles, BVHEntry* out_nodes, int64_t max_nodes);
+int hg_rebuild_mesh(hg_ctx* ctx, int32_t mesh_index, const HalogenTriangle* triangles, int32_t n_triangles,
+                    int32_t leaf_size, int32_t* order, uint64_t geometry_generation);
+int hg_rebuild_mesh_device(hg_ctx* ctx, int32_t mesh_index, const void* d_triangles, int32_t n_triangles,
+                           int32_t leaf_size, void* d_order, uint64_t geometry_generation);
 
 /* Environment cubemap (EnvironmentCubemap, HalgoenCompute.compute:48): RGBA32F texels, layout
  * [mip][face][y][x][4], faces +X,-X,+Y,-Y,+Z,-Z, mip m is max(1, face_size >> m) square.

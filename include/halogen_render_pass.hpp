@@ -253,6 +253,34 @@ class HalogenRenderPass {
         ClearAccumulation();
     }
 
+    // A deformed mesh whose refitted tree no longer fits the pose (not in the reference): a new tree, a linear BVH with
+    // leaves of leaf_size (1..15), built by the host twin (hg_build_blas_lbvh) into the mesh's own slices of the
+    // buffers and by hg_rebuild_mesh on the device, in place, under the buffers' generation.  The mesh's slice of
+    // sc.triangles holds the moved triangles in their current order; afterwards it holds them in the new order, which
+    // is returned (order[k]: the old position of the triangle now at k), and the slice of sc.blas holds the new tree
+    // (2K - 1 entries, which must fit n_nodes; the entries behind them are unreachable padding, so every offset
+    // stays and the next UpdateObjectBuffers is still vouched).  The image starts over.
+    std::vector<int32_t> RebuildMesh(SceneBuffers& sc, int32_t mesh, int32_t n_triangles, int32_t n_nodes,
+                                     int32_t leaf_size) {
+        if (mesh < 0 || size_t(mesh) >= sc.meshes.size()) throw std::runtime_error("RebuildMesh: mesh out of range");
+        const HalogenMeshData& m = sc.meshes[size_t(mesh)];
+        if (n_triangles < 0 || n_nodes < 0 || size_t(m.triangleBufferOffset) + size_t(n_triangles) > sc.triangles.size() ||
+            size_t(m.accelerationBufferOffset) + size_t(n_nodes) > sc.blas.size())
+            throw std::runtime_error("RebuildMesh: slice out of range");
+        HalogenTriangle* tris = sc.triangles.data() + m.triangleBufferOffset;
+        BVHEntry* blas = sc.blas.data() + m.accelerationBufferOffset;
+        const std::vector<HalogenTriangle> moved(tris, tris + n_triangles);
+        std::vector<int32_t> order(static_cast<size_t>(n_triangles));
+        std::vector<BVHEntry> nodes(static_cast<size_t>(n_nodes));
+        const int64_t n = hg_build_blas_lbvh(moved.data(), n_triangles, leaf_size, order.data(), tris, nodes.data(), n_nodes);
+        if (n < 0) throw std::runtime_error("RebuildMesh: hg_build_blas_lbvh failed (the tree must fit the mesh's entries)");
+        std::copy(nodes.begin(), nodes.end(), blas);  // (value-initialised behind the tree: unreachable padding)
+        check(hg_rebuild_mesh(ctx_, mesh, moved.data(), n_triangles, leaf_size, nullptr, sc.geometry_generation),
+              "hg_rebuild_mesh");
+        ClearAccumulation();
+        return order;
+    }
+
     // RP:270-357.  One Execute per frame in the reference; n_frames > 1 runs that many frames in one dispatch with
     // the identical per-frame semantics (FrameCount advancing, the same blend) as long as nothing changes between.
     void Execute(const SceneBuffers& scene, const Camera& camera, int32_t n_frames = 1) {
