@@ -218,6 +218,17 @@ public static class HalogenNative
         int nTriangles, int leafSize, [Out] int[] order, ulong geometryGeneration);
     [DllImport(Lib)] public static extern int hg_rebuild_mesh_device(IntPtr ctx, int meshIndex, IntPtr dTriangles,
         int nTriangles, int leafSize, IntPtr dOrder, ulong geometryGeneration);
+    // The rebuild with leaves chosen by surface area: the radix tree over single triangles, every subtree of at most 15
+    // triangles made one leaf where that is no dearer at nodeCost per inner node against 1 per leaf triangle (0: the
+    // library's value, doubled until the records fit).  hg_build_blas_lbvh_sah is its host twin: maxRecords plays the
+    // device capacity (negative: none), outNodeCost gets the cost used; 2 * nTriangles - 1 entries always suffice.
+    [DllImport(Lib)] public static extern long hg_build_blas_lbvh_sah(HalogenTriangle[] triangles, int nTriangles,
+        float nodeCost, long maxRecords, [Out] int[] outOrder, [Out] HalogenTriangle[] outTriangles,
+        [Out] BVHEntry[] outNodes, long maxNodes, out float outNodeCost);
+    [DllImport(Lib)] public static extern int hg_rebuild_mesh_sah(IntPtr ctx, int meshIndex, HalogenTriangle[] triangles,
+        int nTriangles, float nodeCost, [Out] int[] order, ulong geometryGeneration);
+    [DllImport(Lib)] public static extern int hg_rebuild_mesh_sah_device(IntPtr ctx, int meshIndex, IntPtr dTriangles,
+        int nTriangles, float nodeCost, IntPtr dOrder, ulong geometryGeneration);
 
     // Multi-GPU gather (one context per GPU; the render pass keeps one HalogenRenderPass per device and gathers the
     // tiles to the display device once per displayed image).

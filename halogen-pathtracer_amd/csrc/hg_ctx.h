@@ -62,6 +62,8 @@ struct hg_ctx {
         DevBuf points, partial, bounds;       // key points (3 floats each); per-workgroup and final pmin / pmax
         DevBuf codes, index, codes_sorted, index_sorted, sort_temp;
         DevBuf tris, refs;                    // the triangles in the new order; the compact (refA, refB) per record
+        // hg_rebuild_mesh_sah: the L = 1 tree (an HgLbvhNode per internal node), its live flags, their exclusive scan
+        DevBuf topo, live, new_index, scan_temp;
     } lbvh;
     uint64_t scene_rebuilds = 0;
 

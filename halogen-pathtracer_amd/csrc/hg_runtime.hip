@@ -254,7 +254,8 @@ void hg_destroy(hg_ctx* c) {
                       &c->acc, &c->counters_dev, &c->spill, &c->lost, &c->query_in, &c->query_out, &c->guide0,
                       &c->guide1, &c->denoise_work[0], &c->denoise_work[1], &c->refit_in, &c->refit_raw, &c->lbvh.points,
                       &c->lbvh.partial, &c->lbvh.bounds, &c->lbvh.codes, &c->lbvh.index, &c->lbvh.codes_sorted,
-                      &c->lbvh.index_sorted, &c->lbvh.sort_temp, &c->lbvh.tris, &c->lbvh.refs})
+                      &c->lbvh.index_sorted, &c->lbvh.sort_temp, &c->lbvh.tris, &c->lbvh.refs, &c->lbvh.topo,
+                      &c->lbvh.live, &c->lbvh.new_index, &c->lbvh.scan_temp})
         release(*b);
     refit_reset(c);
     // The trace streams first, the server's stream after them: destroyed before them, the next hipStreamDestroy of a

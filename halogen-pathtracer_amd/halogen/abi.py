@@ -161,6 +161,7 @@ EXPORTS = [
     "hg_comm_assemble_host",
     "hg_refit_blas", "hg_refit_mesh", "hg_refit_mesh_device", "hg_scene_readback",
     "hg_build_blas_lbvh", "hg_rebuild_mesh", "hg_rebuild_mesh_device",
+    "hg_build_blas_lbvh_sah", "hg_rebuild_mesh_sah", "hg_rebuild_mesh_sah_device",
 ]
 # hg_scene_readback: the device scene's arrays (layouts private to the library, csrc/hg_layout.h)
 HG_SCENE_NODES, HG_SCENE_LEAVES, HG_SCENE_TRIS, HG_SCENE_NORMALS, HG_SCENE_MESHES = 0, 1, 2, 3, 4
@@ -245,6 +246,9 @@ def lib() -> C.CDLL:
         "hg_build_blas_lbvh": (i64, [P, i32, i32, P, P, P, i64]),
         "hg_rebuild_mesh": (C.c_int, [P, i32, P, i32, i32, P, C.c_uint64]),
         "hg_rebuild_mesh_device": (C.c_int, [P, i32, P, i32, i32, P, C.c_uint64]),
+        "hg_build_blas_lbvh_sah": (i64, [P, i32, C.c_float, i64, P, P, P, i64, f32p]),
+        "hg_rebuild_mesh_sah": (C.c_int, [P, i32, P, i32, C.c_float, P, C.c_uint64]),
+        "hg_rebuild_mesh_sah_device": (C.c_int, [P, i32, P, i32, C.c_float, P, C.c_uint64]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -485,6 +489,18 @@ class Context:
         Returns the new order: order[k] is the index, in `triangles`, of the triangle now at position k; a torch int32
         tensor on the device for a torch tensor, a numpy int32 array otherwise.  The mesh's triangles are in that order
         from now on (later refit_mesh / rebuild_mesh calls, hg_ray_hit.primitive).  The accumulation is not cleared."""
+        return self._rebuild("hg_rebuild_mesh", mesh_index, triangles, int(leaf_size), generation)
+
+    def rebuild_mesh_sah(self, mesh_index: int, triangles, node_cost: float = 0.0, generation: int = 0):
+        """rebuild_mesh with leaves chosen by surface area (hg_rebuild_mesh_sah, hg_rebuild_mesh_sah_device): the radix
+        tree over single triangles, every subtree of at most 15 triangles made one leaf where that is no dearer at
+        `node_cost` per inner node against 1 per leaf triangle (0: the library's value, doubled until the records fit
+        the tree's capacity).  Arguments, the returned order and everything else as rebuild_mesh."""
+        return self._rebuild("hg_rebuild_mesh_sah", mesh_index, triangles, float(node_cost), generation)
+
+    def _rebuild(self, name, mesh_index, triangles, arg, generation):
+        """hg_rebuild_mesh / hg_rebuild_mesh_sah (`arg`: the leaf size / the node cost), or the _device form for a
+        torch tensor."""
         if hasattr(triangles, "data_ptr") and not isinstance(triangles, np.ndarray):
             import torch
 
@@ -493,9 +509,9 @@ class Context:
                 raise ValueError(f"device triangles must be a contiguous (n, 18) float32 tensor on cuda:{self.device}")
             order = torch.empty(triangles.shape[0], dtype=torch.int32, device=triangles.device)
             torch.cuda.current_stream(triangles.device).synchronize()  # the triangles are complete before the call
-            self._check(lib().hg_rebuild_mesh_device(self._h, int(mesh_index), C.c_void_p(triangles.data_ptr()),
-                                                     triangles.shape[0], int(leaf_size), C.c_void_p(order.data_ptr()),
-                                                     int(generation)), "hg_rebuild_mesh_device")
+            self._check(getattr(lib(), name + "_device")(self._h, int(mesh_index), C.c_void_p(triangles.data_ptr()),
+                                                         triangles.shape[0], arg, C.c_void_p(order.data_ptr()),
+                                                         int(generation)), name + "_device")
             return order
         if isinstance(triangles, np.ndarray):
             a = np.ascontiguousarray(triangles)
@@ -505,8 +521,8 @@ class Context:
         else:
             n, keep = len(triangles), triangles
         order = np.zeros(n, dtype=np.int32)
-        self._check(lib().hg_rebuild_mesh(self._h, int(mesh_index), _ptr(keep), n, int(leaf_size), _ptr(order),
-                                          int(generation)), "hg_rebuild_mesh")
+        self._check(getattr(lib(), name)(self._h, int(mesh_index), _ptr(keep), n, arg, _ptr(order), int(generation)),
+                    name)
         return order
 
     def scene_readback(self, which) -> np.ndarray:
@@ -696,6 +712,26 @@ def build_blas_lbvh(triangles, leaf_size: int):
     if n == 0 or rc != len(nodes):
         raise HalogenError(f"hg_build_blas_lbvh failed ({rc}): no triangles, or leaf_size outside 1..15", int(rc))
     return order[:n], out, nodes
+
+
+def build_blas_lbvh_sah(triangles, node_cost: float = 0.0, max_records: int = -1):
+    """hg_build_blas_lbvh_sah, the host twin of Context.rebuild_mesh_sah: one mesh's triangles (a ctypes array of
+    HalogenTriangle) -> (order, triangles in that order, nodes, the node cost used).  max_records plays the device
+    tree's capacity (negative: no limit); node_cost 0 climbs the library's ladder until the records fit.  The tree has
+    its root at entry 0 and 2M + 1 entries for M inner nodes.  Needs no GPU."""
+    n = len(triangles)
+    order = np.zeros(max(n, 1), dtype=np.int32)
+    out = (HalogenTriangle * max(n, 1))()
+    nodes = (BVHEntry * (2 * max(n, 1) - 1))()
+    used = C.c_float(0.0)
+    rc = lib().hg_build_blas_lbvh_sah(_ptr(triangles), n, float(node_cost), int(max_records), _ptr(order), _ptr(out),
+                                      _ptr(nodes), len(nodes), C.byref(used))
+    if rc < 1:
+        raise HalogenError(f"hg_build_blas_lbvh_sah failed ({rc}): no triangles, a node cost that is negative or not "
+                           f"finite, or more than {max_records} records", int(rc))
+    fit = (BVHEntry * rc)()
+    C.memmove(fit, nodes, C.sizeof(fit))
+    return order[:n], out, fit, used.value
 
 
 def pack_display(rgba: np.ndarray, fmt: int) -> np.ndarray:

@@ -233,7 +233,10 @@ class HalogenRenderPass:
                 # there; both under the current generation, so the upload below stays vouched
                 for i, m in enumerate(scene.meshes):
                     if rebuilds[i] != self._rebuild_serials[i]:
-                        self.ctx.rebuild_mesh(i, m.rebuild_input, m.rebuild_leaf, self._geometry[1])
+                        if m.rebuild_node_cost is not None:  # deform(rebuild="sah")
+                            self.ctx.rebuild_mesh_sah(i, m.rebuild_input, m.rebuild_node_cost, self._geometry[1])
+                        else:
+                            self.ctx.rebuild_mesh(i, m.rebuild_input, m.rebuild_leaf, self._geometry[1])
                         if serials[i] != m.rebuild_at:
                             self.ctx.refit_mesh(i, m.packed_triangles, self._geometry[1])
                     elif serials[i] != self._deform_serials[i]:

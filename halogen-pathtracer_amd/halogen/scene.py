@@ -120,6 +120,7 @@ class RayTracingMesh:
         # deform(rebuild=True) calls, and of the last one: its input (the moved triangles in the order before it, which
         # is the device's until the pass rebuilds), its leaf size, and deform_serial right after it
         self.rebuild_serial, self.rebuild_input, self.rebuild_leaf, self.rebuild_at = 0, None, 0, 0
+        self.rebuild_node_cost = None  # of a deform(rebuild="sah"): the node cost its twin used
         self._cache()
 
     def _cache(self):
@@ -156,7 +157,7 @@ class RayTracingMesh:
         if rc != 0:
             raise abi.HalogenError(f"hg_pack_triangles failed for {self.name}: {rc}")
 
-    def deform(self, vertices, normals=None, rebuild: bool = False, leaf_size: int = 0) -> None:
+    def deform(self, vertices, normals=None, rebuild=False, leaf_size: int = 0, node_cost: float = 0.0) -> None:
         """Move the vertices (same count; skinning, cloth, a morph target) and keep the topology: the triangles are
         repacked through the index list the BLAS build already permuted, and the BLAS is refitted on the host
         (hg_refit_blas: every box from the moved triangles, the tree as it was), so pack() is always current.  The
@@ -170,13 +171,35 @@ class RayTracingMesh:
         has for it, whether or not a full upload came in between, so the room never grows back after a rebuild with
         larger leaves; a leaf size that does not fit raises ValueError before anything is changed.  The triangle order changes: the index list is permuted with it, so later plain deforms repack in
         the new order.  The BVH array keeps its length (entries past the new tree are unreachable padding) and the cache
-        token stays, so the pass rebuilds on the device (rebuild_serial) and its next upload is still vouched."""
+        token stays, so the pass rebuilds on the device (rebuild_serial) and its next upload is still vouched.
+
+        rebuild="sah" is the rebuild with leaves chosen by surface area (abi.build_blas_lbvh_sah, the host twin of
+        Context.rebuild_mesh_sah) at node_cost (0: the library's value, doubled until the tree fits), under the same
+        rule of fit; rebuild_node_cost keeps the cost the twin used, which is what the pass gives the device."""
         v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         n = self.normals if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
         if v.shape != self.vertices.shape or n.shape != v.shape:
             raise ValueError("deform keeps the vertex count")
         fit = []
-        if rebuild and len(self.triangles):
+        sah = None
+        if isinstance(rebuild, str):
+            if rebuild != "sah":
+                raise ValueError(f"rebuild must be False, True or 'sah', not {rebuild!r}")
+            if len(self.triangles):
+                n_tris = len(self.triangles)
+                moved = (abi.HalogenTriangle * n_tris)()
+                rc = abi.lib().hg_pack_triangles(v.ctypes.data, n.ctypes.data, len(v), self.triangles.ctypes.data, n_tris,
+                                                 C.cast(moved, C.c_void_p))
+                if rc != 0:
+                    raise abi.HalogenError(f"hg_pack_triangles failed for {self.name}: {rc}")
+                try:
+                    sah = abi.build_blas_lbvh_sah(moved, node_cost, self.bvh_inner)
+                except abi.HalogenError as e:
+                    if e.rc != abi.HG_E_UNSUPPORTED:
+                        raise
+                    raise ValueError(f"{self.name}: no tree at node cost {node_cost or 'automatic'} fits the "
+                                     f"{self.bvh_inner} inner entries of its tree") from None
+        elif rebuild and len(self.triangles):
             n_tris = len(self.triangles)
             sizes = [int(leaf_size)] if leaf_size else range(4, 16)
             fit = [k for k in sizes if 1 <= k <= 15 and (n_tris + k - 1) // k - 1 <= self.bvh_inner]
@@ -198,6 +221,16 @@ class RayTracingMesh:
             self.bvh_inner = (n_tris + fit[0] - 1) // fit[0] - 1
             self.rebuild_serial += 1
             self.rebuild_input, self.rebuild_leaf, self.rebuild_at = moved, fit[0], self.deform_serial + 1
+            self.rebuild_node_cost = None
+        elif sah:
+            order, self.packed_triangles, nodes, used = sah
+            self.triangles = np.ascontiguousarray(self.triangles[order])
+            C.memset(self.bvh, 0, C.sizeof(self.bvh))
+            C.memmove(self.bvh, nodes, C.sizeof(nodes))
+            self.bvh_inner = (len(nodes) - 1) // 2
+            self.rebuild_serial += 1
+            self.rebuild_input, self.rebuild_leaf, self.rebuild_at = moved, 0, self.deform_serial + 1
+            self.rebuild_node_cost = used  # the rung the twin used: the device is given it, not its own ladder
         elif len(self.triangles):
             abi.refit_blas(self.packed_triangles, self.bvh)
         self.deform_serial += 1

@@ -15,7 +15,8 @@
  *     - Dispose / Release                RP:410-423              -> hg_destroy
  *   plus what the reference never had: readback, counters, error text, multi-GPU tiling, ray queries, the denoised
  *   display, and deforming meshes (hg_refit_mesh: a device refit of one mesh's triangles and BVH boxes;
- *   hg_rebuild_mesh: a new tree for one mesh, built on the device in place).
+ *   hg_rebuild_mesh: a new tree for one mesh, built on the device in place; hg_rebuild_mesh_sah: the same with leaves
+ *   chosen by surface area).
  *
  * The host structs below are byte-identical to the reference's C# blittable structs
  * (RP:10-76, strides from Marshal.SizeOf at RP:163-167): a C# caller passes its List<T>.ToArray()
@@ -403,6 +404,42 @@ int hg_rebuild_mesh(hg_ctx* ctx, int32_t mesh_index, const HalogenTriangle* tria
                     int32_t leaf_size, int32_t* order, uint64_t geometry_generation);
 int hg_rebuild_mesh_device(hg_ctx* ctx, int32_t mesh_index, const void* d_triangles, int32_t n_triangles,
                            int32_t leaf_size, void* d_order, uint64_t geometry_generation);
+
+/* ----------------------------------------------------------------------------------------------
+ * A REBUILD WITH LEAVES CHOSEN BY SURFACE AREA: the second kind of rebuilt tree, beside the fixed-leaf-size one above,
+ * which it leaves as it is.  The same Morton order and Karras' radix tree over single triangles (leaf size 1); then
+ * every subtree of at most 15 triangles becomes one leaf where, by the surface area heuristic on the triangles' raw
+ * boxes, a leaf of N triangles (cost area * N) is no dearer than the subtree (node_cost * area + its children's best
+ * costs).  csrc/hg_lbvh.h fixes the arithmetic, its association and the NaN rule, so the host twin
+ * hg_build_blas_lbvh_sah and the device make the same decisions from the same floats.  The surviving inner nodes keep
+ * their relative order and take the first records of the tree's range; leaves are inline refs of 1..15 triangles; boxes
+ * are the refit's.  A larger node_cost gives larger leaves and fewer records.
+ *
+ * hg_rebuild_mesh_sah / hg_rebuild_mesh_sah_device: hg_rebuild_mesh's arguments, capacity, order, flush, quiesce, guide
+ * images, accumulation, upload rule and stack depth, with `node_cost` in place of `leaf_size`.  node_cost > 0 is taken
+ * as given; 0 starts at HG_LBVH_SAH_NODE_COST (csrc/hg_lbvh.h) and doubles it, at most 6 times, until the records fit
+ * the tree's capacity.  A fixed-leaf-size rebuild after this one, and the reverse, work within the same capacity.
+ * Refused, with text in hg_last_error and the device scene untouched (the record count is known only after the collapse,
+ * which runs in scratch memory): everything hg_rebuild_mesh refuses for its other arguments; a node_cost that is
+ * negative or not finite (HG_E_INVALID); more records than the capacity at the given node_cost, or at the last rung of
+ * the ladder (HG_E_UNSUPPORTED).
+ *
+ * hg_build_blas_lbvh_sah: the host twin.  `max_records` plays the device capacity (negative: no limit);
+ * `out_node_cost` (optional) gets the node cost used.  Out: order, triangles in that order, and the tree in the
+ * reference's format: root at entry 0, the children of the surviving inner node with new index j at entries 1 + 2j and
+ * 2 + 2j (the device's record of that node is the tree's first record + j), 2M + 1 entries for M such nodes, boxes by
+ * hg_refit_blas, depth at most 30 + bits(n - 1) <= 57.  hg_upload_scene accepts the result.  Returns the entry count,
+ * -(count + 1) if max_nodes is too small (2 * n_triangles - 1 always suffices), HG_E_INVALID (a null array, n_triangles
+ * < 1 or > 2^27, a node_cost that is negative or not finite) or HG_E_UNSUPPORTED (more than max_records records);
+ * nothing is written on a refusal.
+ * -------------------------------------------------------------------------------------------- */
+int64_t hg_build_blas_lbvh_sah(const HalogenTriangle* triangles, int32_t n_triangles, float node_cost,
+                               int64_t max_records, int32_t* out_order, HalogenTriangle* out_triangles,
+                               BVHEntry* out_nodes, int64_t max_nodes, float* out_node_cost);
+int hg_rebuild_mesh_sah(hg_ctx* ctx, int32_t mesh_index, const HalogenTriangle* triangles, int32_t n_triangles,
+                        float node_cost, int32_t* order, uint64_t geometry_generation);
+int hg_rebuild_mesh_sah_device(hg_ctx* ctx, int32_t mesh_index, const void* d_triangles, int32_t n_triangles,
+                               float node_cost, void* d_order, uint64_t geometry_generation);
 
 /* Environment cubemap (EnvironmentCubemap, HalgoenCompute.compute:48): RGBA32F texels, layout
  * [mip][face][y][x][4], faces +X,-X,+Y,-Y,+Z,-Z, mip m is max(1, face_size >> m) square.

@@ -1,0 +1,393 @@
+"""hg_build_blas_lbvh_sah, the host twin of the device rebuild with leaves chosen by surface area, against an independent
+numpy fp32 restatement of the second contract in csrc/hg_lbvh.h: over hg_build_blas_lbvh(L = 1)'s tree (tests/
+test_lbvh.py has that one against its own restatement), a top-down recursion that forms raw boxes, areas and best costs
+in the contract's association, collapses, numbers the surviving inner nodes in their Karras order and writes the
+entries; boxes by tests/test_refit.py's restatement.  Then the structure of the result, its cost, the node cost ladder,
+the refusals and the host sanitizer program (make asan_lbvh_sah).  The device build is tests/test_gpu_rebuild_sah.py's."""
+import ctypes as C
+import re
+import subprocess
+from functools import lru_cache
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import lbvh_cases
+from halogen import abi
+from halogen.scene import PackedScene
+from test_refit import BVH_DT, as_np, assert_same_nodes, refit_native, refit_numpy, tris_np
+from test_scene_pack import driver, mesh as mesh_record, parse, write_scene  # noqa: F401 (driver: a fixture)
+
+ROOT = Path(__file__).resolve().parents[1]
+PKG = ROOT / "halogen-pathtracer_amd"
+f32 = np.float32
+MAX_LEAF = 15
+HEADER = (PKG / "csrc" / "hg_lbvh.h").read_text()
+START_COST = float(re.search(r"#define HG_LBVH_SAH_NODE_COST ([0-9.]+)f", HEADER).group(1))
+RUNGS = int(re.search(r"#define HG_LBVH_SAH_RUNGS (\d+)u", HEADER).group(1))
+
+
+def nan_inf_triangles(n=60, seed=8):
+    """Random triangles with NaN and Inf coordinates: one NaN corner coordinate (dropped by the raw box), a triangle with
+    no non-NaN z and one with no non-NaN coordinate at all (extent -Inf), an infinite corner (an infinite extent beside
+    finite ones), and a triangle whose every x is +Inf: its extent is Inf - Inf, so its own cost is NaN and so is the
+    inner cost of every node above it, which the NaN rule keeps inner."""
+    c = np.random.default_rng(seed).uniform(-1.0, 1.0, (n, 3, 3)).astype(f32)
+    c[7, 0, 0] = c[8, 1, 1] = np.nan
+    c[9, :, 2] = np.nan
+    c[10, 2, 0] = np.inf
+    c[11, :, 0] = np.inf
+    c[20, :, :] = np.nan
+    return lbvh_cases.from_corners(c)
+
+
+@lru_cache(maxsize=None)
+def case(name):
+    kind, _, arg = name.partition(":")
+    if kind == "random":
+        return lbvh_cases.random_triangles(int(arg), seed=int(arg))
+    if kind == "identical":
+        return lbvh_cases.identical_triangles(40)
+    if kind == "flat":
+        return lbvh_cases.flat_triangles(60, {"1": (1,), "2": (0, 2), "3": (0, 1, 2)}[arg])
+    if kind == "extreme":
+        return lbvh_cases.extreme_triangles(arg)
+    if kind == "nan_inf":
+        return nan_inf_triangles()
+    return lbvh_cases.mesh_triangles(kind)
+
+
+CASES = [f"random:{n}" for n in (1, 2, 3, 15, 16, 17, 31, 257, 1000)] + \
+        ["identical", "flat:1", "flat:2", "flat:3", "extreme:tiny", "extreme:huge", "extreme:denormal", "extreme:overflow",
+         "nan_inf", "plane", "cube", "dragon"]
+NON_FINITE = ("extreme:huge", "extreme:overflow")  # float32 areas overflow: every cost is +Inf
+
+
+# ---- the contract, restated -------------------------------------------------------------------------------------------------
+def area(t18, first, last):
+    """A of the raw box of the sorted triangles [first, last]: min / max from (+inf, -inf) with NaN dropped, then
+    (dx * dy + dy * dz) + dz * dx, one float32 rounding per operation."""
+    p = t18[first:last + 1, :9].reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        lo = np.fmin.reduce(np.vstack([np.full((1, 3), np.inf, f32), p]), axis=0)
+        hi = np.fmax.reduce(np.vstack([np.full((1, 3), -np.inf, f32), p]), axis=0)
+        d = (hi - lo).astype(f32)
+        return f32(f32(f32(d[0] * d[1]) + f32(d[1] * d[2])) + f32(d[2] * d[0]))
+
+
+class Restated:
+    """The tree of the contract from the L = 1 tree `l1` (BVH_DT; the children of internal node i at entries 1 + 2i,
+    2 + 2i) over the sorted triangles t18, at node_cost."""
+
+    def __init__(self, t18, l1, node_cost):
+        self.t, self.l1, self.c = t18, l1, f32(node_cost)
+        self.span, self.best, self.nan_compares = {}, {}, 0
+        self._spans(0)
+        live = []  # internal node indices that survive, found top-down
+        self.leaves = []  # (first, count) of every leaf
+        self.root_leaf = self._visit(0, live)
+        self.leaf_set = frozenset(self.leaves)
+        self.live = sorted(live)
+        new = {i: j for j, i in enumerate(self.live)}
+        self.nodes = np.zeros(2 * len(self.live) + 1, BVH_DT)
+        self._put(0, 0, new)
+        for i in self.live:
+            for k in (0, 1):
+                self._put(1 + 2 * new[i] + k, 1 + 2 * i + k, new)
+
+    def _spans(self, e):
+        """(first, last) of every entry of the L = 1 tree"""
+        stack, post = [e], []
+        while stack:
+            g = stack.pop()
+            post.append(g)
+            if not self.l1["count"][g]:
+                a = int(self.l1["indexA"][g])
+                stack += [a, a + 1]
+        for g in reversed(post):
+            if self.l1["count"][g]:
+                assert self.l1["count"][g] == 1
+                self.span[g] = (int(self.l1["indexA"][g]),) * 2
+            else:
+                a = int(self.l1["indexA"][g])
+                assert self.span[a][1] + 1 == self.span[a + 1][0]
+                self.span[g] = (self.span[a][0], self.span[a + 1][1])
+
+    def _best(self, e):
+        """(best cost, is a leaf at its best) of an entry covering at most 15 triangles"""
+        if e in self.best:
+            return self.best[e]
+        first, last = self.span[e]
+        A = area(self.t, first, last)
+        with np.errstate(all="ignore"):
+            if self.l1["count"][e]:
+                r = (f32(A * f32(1.0)), True)
+            else:
+                a = int(self.l1["indexA"][e])
+                inner = f32(f32(self.c * A) + f32(self._best(a)[0] + self._best(a + 1)[0]))
+                leaf = f32(A * f32(last - first + 1))
+                self.nan_compares += bool(np.isnan(inner) or np.isnan(leaf))
+                r = (leaf, True) if leaf <= inner else (inner, False)
+        self.best[e] = r
+        return r
+
+    def _visit(self, e, live):
+        """True if the entry ends as a leaf"""
+        first, last = self.span[e]
+        if self.l1["count"][e] or (last - first < MAX_LEAF and self._best(e)[1]):
+            self.leaves.append((first, last - first + 1))
+            return True
+        a = int(self.l1["indexA"][e])
+        live.append((a - 1) // 2)
+        self._visit(a, live)
+        self._visit(a + 1, live)
+        return False
+
+    def _put(self, entry, e, new):
+        first, last = self.span[e]
+        if (first, last - first + 1) in self.leaf_set:
+            self.nodes["indexA"][entry], self.nodes["count"][entry] = first, last - first + 1
+        else:
+            self.nodes["indexA"][entry] = 1 + 2 * new[(int(self.l1["indexA"][e]) - 1) // 2]
+
+
+@lru_cache(maxsize=None)
+def l1_tree(name):
+    order, out, nodes = abi.build_blas_lbvh(case(name), 1)
+    return order, tris_np(out), as_np(nodes)
+
+
+@lru_cache(maxsize=None)
+def restated(name, node_cost):
+    _, t18, l1 = l1_tree(name)
+    return Restated(t18, l1, node_cost)
+
+
+@lru_cache(maxsize=None)
+def twin(name, node_cost, max_records=-1):
+    order, out, nodes, used = abi.build_blas_lbvh_sah(case(name), node_cost, max_records)
+    return order, tris_np(out), as_np(nodes), used
+
+
+def walk(nodes):
+    """The deepest entry's depth and the (first, count) of every leaf, by a walk from the root"""
+    deepest, leaves, seen, stack = 0, [], set(), [(0, 0)]
+    while stack:
+        g, d = stack.pop()
+        assert g not in seen and d <= 62, (g, d)
+        seen.add(g)
+        deepest = max(deepest, d)
+        a, cnt = int(nodes["indexA"][g]), int(nodes["count"][g])
+        if cnt:
+            leaves.append((a, cnt))
+        else:
+            stack += [(a + 1, d + 1), (a, d + 1)]
+    assert len(seen) == len(nodes), "every entry is reached"
+    return deepest, leaves
+
+
+def tree_cost(t18, nodes, node_cost):
+    """The SAH cost of a whole tree from raw boxes formed here (not hg_refit_blas's stored boxes): node_cost * A per inner
+    entry, A * N per leaf, with the contract's float32 A (an extent of 1e-30 has no area in float32, and the contract
+    decides on that) and every product and sum in float64."""
+    def box_area(first, count):
+        return np.float64(area(t18, first, first + count - 1))
+
+    total, span, post, stack = 0.0, {}, [], [0]
+    while stack:
+        g = stack.pop()
+        post.append(g)
+        if not nodes["count"][g]:
+            stack += [int(nodes["indexA"][g]), int(nodes["indexA"][g]) + 1]
+    for g in reversed(post):
+        a, cnt = int(nodes["indexA"][g]), int(nodes["count"][g])
+        if cnt:
+            span[g] = (a, cnt)
+            total += box_area(a, cnt) * cnt
+        else:
+            span[g] = (span[a][0], span[a][1] + span[a + 1][1])
+            total += node_cost * box_area(*span[g])
+    return total
+
+
+# ---- the twin equals the restatement ----------------------------------------------------------------------------------------------
+# (the dragon's restatement takes seconds: at one node cost)
+@pytest.mark.parametrize("name,node_cost", [(c, k) for c in CASES for k in (0.5, 2.0) if c != "dragon" or k == 2.0])
+def test_twin_equals_the_restatement(name, node_cost):
+    want_order, t18, l1 = l1_tree(name)
+    n = len(t18)
+    order, out, got, used = twin(name, node_cost)
+    want = restated(name, node_cost)
+    assert used == node_cost
+    assert np.array_equal(order, want_order), "out_order is hg_build_blas_lbvh's"
+    assert out.tobytes() == t18.tobytes()
+    assert len(got) == len(want.nodes) == 2 * len(want.live) + 1, (len(got), len(want.live))
+    assert np.array_equal(got["indexA"], want.nodes["indexA"]) and np.array_equal(got["count"], want.nodes["count"]), name
+    if name == "nan_inf":  # (tests/test_refit.py's restatement is for finite vertices: the boxes against hg_refit_blas)
+        assert want.nan_compares > 0, "the input must reach the NaN rule"
+        assert any(not want.best[e][1] and np.isnan(want.best[e][0]) for e in want.best), "a NaN cost keeps a node inner"
+        assert_same_nodes(refit_native(t18, got), got, name)
+    else:
+        assert_same_nodes(got, refit_numpy(t18, want.nodes), name)
+    # ---- structure
+    depth, leaves = walk(got)
+    leaves.sort()
+    assert sorted(want.leaves) == leaves
+    covered = np.zeros(n, np.int32)
+    for a, cnt in leaves:
+        assert 1 <= cnt <= MAX_LEAF
+        covered[a:a + cnt] += 1
+    assert (covered == 1).all(), "every triangle lies in exactly one leaf"
+    spans = {(f, l - f + 1) for f, l in want.span.values()}
+    assert set(leaves) <= spans, "every leaf is a whole subtree of the L = 1 radix tree"
+    assert depth <= 30 + (n - 1).bit_length() <= 57, (depth, n)
+    if n <= MAX_LEAF and want.root_leaf:
+        assert len(got) == 1 and (got["indexA"][0], got["count"][0]) == (0, n)
+    assert_same_nodes(refit_native(t18, got), got, name + ": hg_refit_blas is the identity")
+
+
+def test_inputs_are_what_they_claim():
+    assert len(case("plane")) == 200 and len(case("cube")) == 12 and len(case("dragon")) == 8712
+    assert np.array_equal(l1_tree("identical")[0], np.arange(40)), "one run of equal keys: the caller's order"
+    # node counts around the largest leaf: 15 may be one leaf, 16 never is
+    assert len(twin("random:16", 2.0)[2]) >= 3 and len(twin("random:17", 1e6)[2]) >= 3
+    assert len(twin("random:15", 1e6)[2]) == 1, "an inner node dearer than anything: 15 triangles are one leaf"
+    assert len(twin("random:15", 1e-6)[2]) == 29, "an inner node for nothing: every triangle its own leaf"
+    # both outcomes occur in one tree
+    got = twin("dragon", 2.0)[2]
+    counts = got["count"][got["count"] > 0]
+    assert counts.min() == 1 and counts.max() > 4 and len(np.unique(counts)) > 5, np.unique(counts)
+
+
+@pytest.mark.parametrize("name", ["plane", "cube", "dragon", "random:1000", "identical"])
+def test_upload_validation_accepts_the_tree(driver, name):
+    """hg_pack_geometry (hg_upload_scene's validation and layout) takes the twin's arrays as they are: every leaf an
+    inline ref, one record per inner entry."""
+    _, t18, got, _ = twin(name, 2.0)
+    nodes = (abi.BVHEntry * len(got)).from_buffer_copy(got.tobytes())
+    packed = PackedScene(spheres=(abi.HalogenSphere * 0)(), meshes=(abi.HalogenMeshData * 1)(mesh_record(0, 0)),
+                         materials=(abi.PackedHalogenMaterial * 1)(), triangles=lbvh_cases.from_rows(t18), blas=nodes)
+    r = parse(driver("pack", write_scene(driver, packed)))
+    M = (len(got) - 1) // 2
+    depth, _ = walk(got)
+    assert r["walk"] == "ok" and int(r["inner"]) == M and int(r["inline"]) == M + 1 and int(r["table"]) == 0, r
+    assert int(r["max_depth"]) == depth, (r, depth)
+
+
+# ---- cost ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [c for c in CASES if c != "nan_inf"])
+def test_collapsing_never_costs_more(name):
+    """The decision is optimal per subtree in float32; summed here in float64, the twin's tree costs no more than the
+    uncollapsed L = 1 tree up to the decisions' rounding: a cost is a sum of non-negative terms formed by at most 3
+    rounded operations per node of a subtree of at most 14 nodes and 15 triangles, so two costs that compare one way in
+    float32 differ the other way by less than 100 * 2^-24 < 1e-5 of their size.  (Areas that overflowed: Inf <= Inf.)"""
+    _, t18, l1 = l1_tree(name)
+    for node_cost in (0.5, 2.0):
+        got = twin(name, node_cost)[2]
+        a, b = tree_cost(t18, got, node_cost), tree_cost(t18, l1, node_cost)
+        print(f"{name} node_cost {node_cost}: collapsed {a:.6g}, L = 1 {b:.6g}")
+        assert np.isfinite(a) == (name not in NON_FINITE) and a <= b * (1 + 1e-5), (name, node_cost, a, b)
+
+
+def test_nan_costs_compare_with_nothing():
+    """The one input left out above: a NaN area makes the whole tree's cost NaN, which is neither more nor less than
+    another; its decisions are test_twin_equals_the_restatement's."""
+    _, t18, l1 = l1_tree("nan_inf")
+    with np.errstate(all="ignore"):
+        assert np.isnan(tree_cost(t18, twin("nan_inf", 2.0)[2], 2.0)) and np.isnan(tree_cost(t18, l1, 2.0))
+
+
+def test_dragon_costs_less_than_leaves_of_four():
+    t18 = l1_tree("dragon")[1]
+    got = twin("dragon", 2.0)[2]
+    l4 = as_np(abi.build_blas_lbvh(case("dragon"), 4)[2])
+    a, b = tree_cost(t18, got, 2.0), tree_cost(t18, l4, 2.0)
+    print(f"dragon at node cost 2: collapsed {a:.6g}, L = 4 {b:.6g}, ratio {a / b:.3f}")
+    assert a < b, (a, b)
+    assert (len(got) - 1) // 2 < 2 * ((len(l4) - 1) // 2), "a record count of the same order"
+
+
+# ---- the ladder and the refusals ---------------------------------------------------------------------------------------------------
+def records(name, node_cost):
+    return (len(twin(name, node_cost)[2]) - 1) // 2
+
+
+def test_ladder():
+    name = "random:1000"
+    m0, m1 = records(name, START_COST), records(name, 2 * START_COST)
+    last_cost = START_COST * 2 ** (RUNGS - 1)
+    m_last = records(name, last_cost)
+    assert m_last > 0 and m1 < m0, (m0, m1, m_last)
+    # automatic, no limit or room enough: the start rung
+    assert twin(name, 0.0)[3] == START_COST and twin(name, 0.0, m0)[3] == START_COST
+    assert twin(name, 0.0)[2].tobytes() == twin(name, START_COST)[2].tobytes()
+    # one record short at the start rung: exactly one rung up
+    order, out, got, used = twin(name, 0.0, m0 - 1)
+    assert used == 2 * START_COST and got.tobytes() == twin(name, 2 * START_COST)[2].tobytes()
+    # the last rung just fits; one record less is refused
+    assert twin(name, 0.0, m_last)[3] <= last_cost
+    with pytest.raises(abi.HalogenError) as e:
+        abi.build_blas_lbvh_sah(case(name), 0.0, m_last - 1)
+    assert e.value.rc == abi.HG_E_UNSUPPORTED
+    # an explicit node cost is taken as given: no ladder
+    with pytest.raises(abi.HalogenError) as e:
+        abi.build_blas_lbvh_sah(case(name), START_COST, m0 - 1)
+    assert e.value.rc == abi.HG_E_UNSUPPORTED
+    assert twin(name, START_COST, m0)[3] == START_COST
+
+
+def test_refusals_write_nothing():
+    tris = case("random:16")
+    L = abi.lib()
+    order = np.full(16, -7, np.int32)
+    out, nodes = (abi.HalogenTriangle * 16)(), (abi.BVHEntry * 31)()
+    used = C.c_float(-3.0)
+    p = lambda a: C.cast(a, C.c_void_p)  # noqa: E731
+
+    def call(n, cost, max_records, cap, t=tris):
+        return L.hg_build_blas_lbvh_sah(p(t) if t is not None else None, n, cost, max_records, order.ctypes.data, p(out),
+                                        p(nodes), cap, C.byref(used))
+
+    m = records("random:16", 1e-6)
+    assert m >= 2
+    for rc, args in ((abi.HG_E_INVALID, (0, 2.0, -1, 31)), (abi.HG_E_INVALID, (-1, 2.0, -1, 31)),
+                     (abi.HG_E_INVALID, (16, -1.0, -1, 31)), (abi.HG_E_INVALID, (16, float("nan"), -1, 31)),
+                     (abi.HG_E_INVALID, (16, float("inf"), -1, 31)), (abi.HG_E_INVALID, (16, 2.0, -1, 31, None)),
+                     (abi.HG_E_UNSUPPORTED, (16, 1e-6, m - 1, 31)), (-(2 * m + 2), (16, 1e-6, -1, 2 * m))):
+        assert call(*args) == rc, args
+    assert (order == -7).all() and not bytes(out).strip(b"\0") and not bytes(nodes).strip(b"\0") and used.value == -3.0
+    assert call(16, 1e-6, m, 31) == 2 * m + 1 and used.value == f32(1e-6)
+    assert L.hg_build_blas_lbvh_sah(p(tris), 16, 2.0, -1, order.ctypes.data, p(out), p(nodes), 31, None) > 0
+
+
+def test_deform_rebuild_sah_keeps_pack_current():
+    """RayTracingMesh.deform(rebuild="sah"): the twin's arrays in the mesh's own slices, the node cost it used kept for
+    the pass; rebuild=True still means the fixed leaf size."""
+    import refit_cases
+    from halogen import scenes
+
+    sc = scenes.cornell_box()
+    mesh = sc.meshes[7]
+    rest, entries, inner = mesh.vertices.copy(), len(mesh.bvh), mesh.bvh_inner
+    mesh.deform(refit_cases.twist(rest, 0.7), rebuild="sah")
+    order, out, nodes, used = abi.build_blas_lbvh_sah(mesh.rebuild_input, 0.0, inner)
+    assert mesh.rebuild_node_cost == used and mesh.rebuild_serial == 1 and len(mesh.bvh) == entries
+    assert bytes(mesh.packed_triangles) == bytes(out) and bytes(mesh.bvh)[:C.sizeof(nodes)] == bytes(nodes)
+    assert mesh.bvh_inner == (len(nodes) - 1) // 2 <= inner
+    sc.pack()
+    mesh.deform(refit_cases.twist(rest, 0.3), rebuild=True)
+    assert mesh.rebuild_node_cost is None and mesh.rebuild_leaf >= 4 and mesh.rebuild_serial == 2
+    with pytest.raises(ValueError):
+        mesh.deform(rest, rebuild="sah", node_cost=1e-6)  # every triangle its own leaf: more records than the tree has
+    with pytest.raises(ValueError):
+        mesh.deform(rest, rebuild="lbvh")
+
+
+# ---- the sanitizer program ------------------------------------------------------------------------------------------------------
+def test_asan_lbvh_sah_program():
+    """host/asan_lbvh_sah.cpp under AddressSanitizer + UBSan: hg_build_blas_lbvh_sah on the input classes above (make
+    asan_lbvh_sah; a stand-alone program, host code only)."""
+    subprocess.run(["make", "-s", "-C", str(PKG), "asan_lbvh_sah"], check=True)
+    r = subprocess.run([str(PKG / "build" / "asan_lbvh_sah")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "asan_lbvh_sah ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
