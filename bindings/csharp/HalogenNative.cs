@@ -229,6 +229,32 @@ public static class HalogenNative
         int nTriangles, float nodeCost, [Out] int[] order, ulong geometryGeneration);
     [DllImport(Lib)] public static extern int hg_rebuild_mesh_sah_device(IntPtr ctx, int meshIndex, IntPtr dTriangles,
         int nTriangles, float nodeCost, IntPtr dOrder, ulong geometryGeneration);
+    // Deforming a mesh from its vertices: hg_set_mesh_vertices binds the mesh's index list (its triangles in their
+    // current order) to its tree on the device, where every rebuild keeps it in step; hg_deform_mesh packs the triangles
+    // there from moved positions and normals and refits (HG_DEFORM_REFIT) or rebuilds (leafSize / nodeCost) from them;
+    // hg_set_mesh_skin / hg_skin_mesh produce the vertices on the device by linear-blend skinning (four uint16 bone
+    // indices and four weights a vertex; a bone is a row-major 3 x 4 matrix, 12 floats).  hg_skin_vertices is the host
+    // twin, hg_mesh_vertices_readback a diagnostic copy of the last skinned vertices.  The binding lives until the next
+    // full upload.
+    public const int HG_DEFORM_REFIT = 0, HG_DEFORM_REBUILD = 1, HG_DEFORM_REBUILD_SAH = 2;
+    [DllImport(Lib)] public static extern int hg_set_mesh_vertices(IntPtr ctx, int meshIndex, int[] indices,
+        int nTriangles, int nVertices);
+    [DllImport(Lib)] public static extern int hg_deform_mesh(IntPtr ctx, int meshIndex, float[] positions,
+        float[] normals, int nVertices, int how, int leafSize, float nodeCost, [Out] int[] order,
+        ulong geometryGeneration);
+    [DllImport(Lib)] public static extern int hg_deform_mesh_device(IntPtr ctx, int meshIndex, IntPtr dPositions,
+        IntPtr dNormals, int nVertices, int how, int leafSize, float nodeCost, IntPtr dOrder, ulong geometryGeneration);
+    [DllImport(Lib)] public static extern int hg_set_mesh_skin(IntPtr ctx, int meshIndex, float[] restPositions,
+        float[] restNormals, ushort[] boneIndices, float[] weights, int nVertices, int nBones);
+    [DllImport(Lib)] public static extern int hg_skin_mesh(IntPtr ctx, int meshIndex, float[] bones, int nBones, int how,
+        int leafSize, float nodeCost, [Out] int[] order, ulong geometryGeneration);
+    [DllImport(Lib)] public static extern int hg_skin_mesh_device(IntPtr ctx, int meshIndex, IntPtr dBones, int nBones,
+        int how, int leafSize, float nodeCost, IntPtr dOrder, ulong geometryGeneration);
+    [DllImport(Lib)] public static extern int hg_skin_vertices(float[] restPositions, float[] restNormals,
+        ushort[] boneIndices, float[] weights, int nVertices, float[] bones, int nBones, [Out] float[] outPositions,
+        [Out] float[] outNormals);
+    [DllImport(Lib)] public static extern int hg_mesh_vertices_readback(IntPtr ctx, int meshIndex,
+        [Out] float[] positions, [Out] float[] normals, int nVertices);
 
     // Multi-GPU gather (one context per GPU; the render pass keeps one HalogenRenderPass per device and gathers the
     // tiles to the display device once per displayed image).

@@ -66,6 +66,20 @@ struct hg_ctx {
         DevBuf topo, live, new_index, scan_temp;
     } lbvh;
     uint64_t scene_rebuilds = 0;
+    // Deform from vertices (hg_set_mesh_vertices, hg_deform_mesh, hg_skin_mesh; hg_deform.hip).  Per bound tree, by its
+    // triangle offset like rebuild_slots, until the next full upload: the mesh's index list on the device in the tree's
+    // current triangle order (every rebuild of the tree permutes it into `spare` and swaps the two), and, once
+    // hg_set_mesh_skin gave them, the rest pose, the influences and the vertices the last hg_skin_mesh* produced.
+    struct VertexBinding {
+        DevBuf indices, spare;  // n_tris int3 each
+        int32_t n_tris = 0, n_vertices = 0;
+        DevBuf rest_positions, rest_normals, bone_indices, weights;  // 3 floats, 3 floats, 4 uint16, 4 floats per vertex
+        DevBuf positions, normals;                                   // the skinned vertices
+        int32_t n_bones = 0;  // 0: no skin
+        bool skinned = false;  // positions / normals hold a pose
+    };
+    std::map<uint32_t, VertexBinding> vertex_bindings;
+    DevBuf deform_positions, deform_normals, deform_bones;  // the host-pointer forms' vertices and palette
 
     // cubemap
     DevBuf cube;

@@ -1,0 +1,385 @@
+// hg_deform.hip — deforming geometry from where its users hold it, the vertices: hg_set_mesh_vertices binds a mesh's index
+// list to its tree on the device, hg_deform_mesh / hg_deform_mesh_device pack the 72-byte triangles from vertex arrays
+// there, hg_set_mesh_skin / hg_skin_mesh / hg_skin_mesh_device produce those vertices by linear-blend skinning (the
+// contract: hg_skin.h; the host twin: hg_skin_vertices, hg_host.cpp).  What follows the pack is hg_refit_mesh_device,
+// hg_rebuild_mesh_device or hg_rebuild_mesh_sah_device on the packed triangles, unchanged.  Not in the reference.
+//
+// Three kernels, all on the context stream and ordered by it alone: no atomics, no kernel that waits on another
+// workgroup.  The kernels first, then the entry points of the C-ABI.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "halogen_abi.h"
+#include "hg_rt.h"
+#include "hg_skin.h"
+#include "hg_tunables.h"
+
+using namespace hgrt;
+
+static_assert(sizeof(HalogenTriangle) == 72, "the pack kernel writes a triangle as 18 floats");
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kTriWords = 18;  // floats of a HalogenTriangle
+
+// Pack: out[t] = the HalogenTriangle of indices[3t .. 3t + 2], byte for byte what hg_pack_triangles writes.  A workgroup
+// takes 256 triangles: its 768 indices are read by consecutive lanes, a lane per corner; each corner's position and
+// normal (two scattered 12-byte reads, the part a gather cannot avoid) go to their places in the triangle's 18 floats in
+// LDS, and the 18 KiB leave as consecutive float4 (`out` is 16-byte aligned and a workgroup's part starts a multiple of
+// 16 bytes into it): the mirror image of hg_refit_repack's read side.  Every index is below the vertex count
+// (hg_set_mesh_vertices checked the list, and only deform_follow_order's permutation has touched it since).
+__global__ __launch_bounds__(kBlock) void hg_deform_pack(const int32_t* __restrict__ indices, uint32_t n_tris,
+                                                         const float* __restrict__ positions,
+                                                         const float* __restrict__ normals, float* __restrict__ out) {
+    __shared__ float4 s_out4[kBlock * kTriWords / 4];
+    float* s_out = reinterpret_cast<float*>(s_out4);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t base = blockIdx.x * uint32_t(kBlock);  // < n_tris: the grid is ceil(n_tris / 256)
+    const uint32_t cnt = min(uint32_t(kBlock), n_tris - base);
+    const int32_t* idx = indices + size_t(base) * 3;
+    for (uint32_t i = tid; i < cnt * 3; i += kBlock) {
+        const size_t v = size_t(uint32_t(idx[i])) * 3;
+        const uint32_t t = i / 3, k = i - 3 * t;
+        float* o = s_out + t * kTriWords + k * 3;  // pointA, pointB, pointC, normalA, normalB, normalC
+        o[0] = positions[v];
+        o[1] = positions[v + 1];
+        o[2] = positions[v + 2];
+        o[9] = normals[v];
+        o[10] = normals[v + 1];
+        o[11] = normals[v + 2];
+    }
+    __syncthreads();
+    const uint32_t words = cnt * kTriWords;
+    float* g = out + size_t(base) * kTriWords;
+    float4* g4 = reinterpret_cast<float4*>(g);
+    for (uint32_t i = tid; i < words / 4; i += kBlock) g4[i] = s_out4[i];
+    for (uint32_t i = (words & ~3u) + tid; i < words; i += kBlock) g[i] = s_out[i];
+}
+
+// Skin: a lane per vertex over hg_skin_vertex.  A workgroup's 256 rest positions and normals (3 KiB each) come in and
+// the results go out through LDS as consecutive words; the influences are one 8-byte and one 16-byte read per lane (the
+// library's own arrays, aligned).  kLds: the palette (n_bones <= HG_SKIN_LDS_BONES) is copied to LDS first; otherwise a
+// lane reads its four bones from global memory.  Every bone index is below n_bones (hg_set_mesh_skin checked them).
+template <bool kLds>
+__global__ __launch_bounds__(kBlock) void hg_deform_skin(const float* __restrict__ rest_positions,
+                                                         const float* __restrict__ rest_normals,
+                                                         const uint2* __restrict__ bone_indices,
+                                                         const float4* __restrict__ weights, uint32_t n_vertices,
+                                                         const float* __restrict__ bones, uint32_t n_bones,
+                                                         float* __restrict__ out_positions,
+                                                         float* __restrict__ out_normals) {
+    __shared__ float s_p[kBlock * 3];
+    __shared__ float s_n[kBlock * 3];
+    __shared__ float s_bones[kLds ? HG_SKIN_LDS_BONES * HG_SKIN_BONE_FLOATS : 1];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t base = blockIdx.x * uint32_t(kBlock);  // < n_vertices: the grid is ceil(n_vertices / 256)
+    const uint32_t cnt = min(uint32_t(kBlock), n_vertices - base);
+    const size_t off = size_t(base) * 3;
+    for (uint32_t i = tid; i < cnt * 3; i += kBlock) {
+        s_p[i] = rest_positions[off + i];
+        s_n[i] = rest_normals[off + i];
+    }
+    if (kLds)
+        for (uint32_t i = tid; i < n_bones * HG_SKIN_BONE_FLOATS; i += kBlock) s_bones[i] = bones[i];
+    __syncthreads();
+    if (tid < cnt) {
+        const uint2 bi = bone_indices[base + tid];
+        const float4 wv = weights[base + tid];
+        const uint16_t idx[4] = {uint16_t(bi.x & 0xFFFFu), uint16_t(bi.x >> 16), uint16_t(bi.y & 0xFFFFu),
+                                 uint16_t(bi.y >> 16)};
+        const float w[4] = {wv.x, wv.y, wv.z, wv.w};
+        const float p[3] = {s_p[tid * 3], s_p[tid * 3 + 1], s_p[tid * 3 + 2]};
+        const float n[3] = {s_n[tid * 3], s_n[tid * 3 + 1], s_n[tid * 3 + 2]};
+        float op[3], on[3];
+        hg_skin_vertex(kLds ? s_bones : bones, idx, w, p, n, op, on);
+        for (int k = 0; k < 3; ++k) {  // (the lane's own three words)
+            s_p[tid * 3 + k] = op[k];
+            s_n[tid * 3 + k] = on[k];
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < cnt * 3; i += kBlock) {
+        out_positions[off + i] = s_p[i];
+        out_normals[off + i] = s_n[i];
+    }
+}
+
+// The bound index list after a rebuild: dst[k] = src[order[k]], an int3 per lane (order[k] < n_tris: a permutation)
+__global__ __launch_bounds__(kBlock) void hg_deform_permute(const int32_t* __restrict__ src,
+                                                            const uint32_t* __restrict__ order, uint32_t n_tris,
+                                                            int32_t* __restrict__ dst) {
+    const uint32_t k = blockIdx.x * uint32_t(kBlock) + threadIdx.x;
+    if (k >= n_tris) return;
+    const int32_t* s = src + size_t(order[k]) * 3;
+    const int32_t a = s[0], b = s[1], c2 = s[2];
+    int32_t* d = dst + size_t(k) * 3;
+    d[0] = a;
+    d[1] = b;
+    d[2] = c2;
+}
+
+void release_binding(hg_ctx::VertexBinding& b) {
+    for (DevBuf* d : {&b.indices, &b.spare, &b.rest_positions, &b.rest_normals, &b.bone_indices, &b.weights, &b.positions,
+                      &b.normals})
+        release(*d);
+}
+
+// The scene, the mesh and its binding, for the entry point `who`
+int binding_of(hg_ctx* c, const char* who, int32_t mesh_index, hg_ctx::VertexBinding*& b) {
+    if (!c->has_scene) return fail(c, HG_E_NOSCENE, "%s: hg_upload_scene not called", who);
+    if (mesh_index < 0 || mesh_index >= c->n_meshes)
+        return fail(c, HG_E_INVALID, "%s: mesh_index %d out of range (%d meshes)", who, mesh_index, c->n_meshes);
+    auto it = c->vertex_bindings.find(c->dev_meshes[size_t(mesh_index)].tri_offset);
+    if (it == c->vertex_bindings.end())
+        return fail(c, HG_E_INVALID, "%s: mesh %d has no vertex binding (hg_set_mesh_vertices; a full upload drops it)", who,
+                    mesh_index);
+    b = &it->second;
+    return HG_OK;
+}
+
+// What hg_deform_mesh* check beyond the binding, before the first launch
+int deform_check(hg_ctx* c, const char* who, int32_t mesh_index, const void* positions, const void* normals,
+                 int32_t n_vertices, int32_t how, hg_ctx::VertexBinding*& b) {
+    if (int rc = binding_of(c, who, mesh_index, b)) return rc;
+    if (!positions || !normals) return fail(c, HG_E_INVALID, "%s: null position or normal array", who);
+    if (n_vertices != b->n_vertices)
+        return fail(c, HG_E_INVALID, "%s: mesh %d: %d vertices, its binding holds %d", who, mesh_index, n_vertices,
+                    b->n_vertices);
+    if (how != HG_DEFORM_REFIT && how != HG_DEFORM_REBUILD && how != HG_DEFORM_REBUILD_SAH)
+        return fail(c, HG_E_INVALID, "%s: unknown kind of deform %d", who, how);
+    return HG_OK;
+}
+
+// The pack into the context's triangle buffer, then the refit or rebuild of the mesh from it: the device entry point
+// itself, with its own checks, flush (nothing is held any more), quiesce and bookkeeping.  d_positions, d_normals:
+// n_vertices * 3 floats on the device, 4-byte aligned, complete.  A rebuild leaves its order in c->lbvh.index_sorted.
+int deform_device(hg_ctx* c, int32_t mesh_index, const hg_ctx::VertexBinding& b, const void* d_positions,
+                  const void* d_normals, int32_t how, int32_t leaf_size, float node_cost, void* d_order,
+                  uint64_t geometry_generation) {
+    const int32_t n_tris = b.n_tris;
+    if (int rc = set_device(c)) return rc;
+    if (int rc = ensure(c, c->refit_in, size_t(n_tris) * sizeof(HalogenTriangle))) return rc;
+    hipLaunchKernelGGL(hg_deform_pack, dim3(uint32_t((n_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                       static_cast<const int32_t*>(b.indices.p), uint32_t(n_tris), static_cast<const float*>(d_positions),
+                       static_cast<const float*>(d_normals), static_cast<float*>(c->refit_in.p));
+    HG_HIP(c, hipGetLastError());
+    if (how == HG_DEFORM_REBUILD)
+        return hg_rebuild_mesh_device(c, mesh_index, c->refit_in.p, n_tris, leaf_size, d_order, geometry_generation);
+    if (how == HG_DEFORM_REBUILD_SAH)
+        return hg_rebuild_mesh_sah_device(c, mesh_index, c->refit_in.p, n_tris, node_cost, d_order, geometry_generation);
+    return hg_refit_mesh_device(c, mesh_index, c->refit_in.p, n_tris, geometry_generation);
+}
+
+// A host array to a context-owned device buffer, on the context stream
+int stage(hg_ctx* c, DevBuf& buf, const void* src, size_t bytes) {
+    if (int rc = set_device(c)) return rc;
+    if (int rc = ensure(c, buf, bytes)) return rc;
+    HG_HIP(c, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return HG_OK;
+}
+
+int order_to_host(hg_ctx* c, int32_t how, int32_t* order, int32_t n_tris) {
+    if (order && how != HG_DEFORM_REFIT)
+        HG_HIP(c, hipMemcpy(order, c->lbvh.index_sorted.p, size_t(n_tris) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return HG_OK;
+}
+
+// What hg_skin_mesh* check before the first launch
+int skin_check(hg_ctx* c, const char* who, int32_t mesh_index, const void* bones, int32_t n_bones, int32_t how,
+               hg_ctx::VertexBinding*& b) {
+    if (int rc = binding_of(c, who, mesh_index, b)) return rc;
+    if (b->n_bones == 0) return fail(c, HG_E_INVALID, "%s: mesh %d has no skin (hg_set_mesh_skin)", who, mesh_index);
+    if (!bones) return fail(c, HG_E_INVALID, "%s: null bone palette", who);
+    if (n_bones != b->n_bones)
+        return fail(c, HG_E_INVALID, "%s: mesh %d: %d bones, its skin was bound with %d", who, mesh_index, n_bones, b->n_bones);
+    if (how != HG_DEFORM_REFIT && how != HG_DEFORM_REBUILD && how != HG_DEFORM_REBUILD_SAH)
+        return fail(c, HG_E_INVALID, "%s: unknown kind of deform %d", who, how);
+    return HG_OK;
+}
+
+// The skin kernel into the binding's vertex buffers, then the path of hg_deform_mesh_device from them
+int skin_device(hg_ctx* c, int32_t mesh_index, hg_ctx::VertexBinding& b, const void* d_bones, int32_t how,
+                int32_t leaf_size, float node_cost, void* d_order, uint64_t geometry_generation) {
+    if (int rc = set_device(c)) return rc;
+    const uint32_t nv = uint32_t(b.n_vertices);
+    const dim3 grid((nv + kBlock - 1) / kBlock);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, c->stream, static_cast<const float*>(b.rest_positions.p),
+                           static_cast<const float*>(b.rest_normals.p), static_cast<const uint2*>(b.bone_indices.p),
+                           static_cast<const float4*>(b.weights.p), nv, static_cast<const float*>(d_bones),
+                           uint32_t(b.n_bones), static_cast<float*>(b.positions.p), static_cast<float*>(b.normals.p));
+    };
+    if (b.n_bones <= HG_SKIN_LDS_BONES)
+        launch(hg_deform_skin<true>);
+    else
+        launch(hg_deform_skin<false>);
+    HG_HIP(c, hipGetLastError());
+    b.skinned = true;
+    return deform_device(c, mesh_index, b, b.positions.p, b.normals.p, how, leaf_size, node_cost, d_order,
+                         geometry_generation);
+}
+
+}  // namespace
+
+namespace hgrt {
+
+int deform_follow_order(hg_ctx* c, uint32_t tri_offset, const uint32_t* d_order, uint32_t n_tris) {
+    auto it = c->vertex_bindings.find(tri_offset);
+    if (it == c->vertex_bindings.end()) return HG_OK;
+    hg_ctx::VertexBinding& b = it->second;
+    if (uint32_t(b.n_tris) != n_tris)  // (a rebuild takes the tree's extent, which is what was bound)
+        return fail(c, HG_E_INVALID, "hg_rebuild_mesh: the bound index list holds %d triangles, the rebuild %u", b.n_tris, n_tris);
+    if (int rc = ensure(c, b.spare, size_t(n_tris) * 3 * sizeof(int32_t))) return rc;
+    hipLaunchKernelGGL(hg_deform_permute, dim3((n_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
+                       static_cast<const int32_t*>(b.indices.p), d_order, n_tris, static_cast<int32_t*>(b.spare.p));
+    HG_HIP(c, hipGetLastError());
+    std::swap(b.indices, b.spare);
+    return HG_OK;
+}
+
+}  // namespace hgrt
+
+extern "C" {
+
+int hg_set_mesh_vertices(hg_ctx* c, int32_t mesh_index, const int32_t* indices, int32_t n_tris, int32_t n_vertices) {
+    static const char* who = "hg_set_mesh_vertices";
+    if (!c) return HG_E_INVALID;
+    if (int rc = hg_ctx_flush(c)) return rc;
+    if (c->has_scene && !indices) return fail(c, HG_E_INVALID, "%s: null index array", who);
+    hg_ctx::RefitTree* tree = nullptr;
+    std::vector<int32_t> instances;
+    if (int rc = refit_check(c, mesh_index, indices, n_tris, tree, instances)) return rc;
+    if (n_tris == 0 || uint32_t(n_tris) != tree->plan.extent)
+        return fail(c, HG_E_INVALID, "%s: mesh %d: %d triangles, its tree holds %u", who, mesh_index, n_tris,
+                    tree->plan.extent);
+    if (n_vertices <= 0) return fail(c, HG_E_INVALID, "%s: mesh %d: %d vertices", who, mesh_index, n_vertices);
+    const int64_t bad = hg_skin_first_bad_index(indices, n_tris, n_vertices);
+    if (bad >= 0)
+        return fail(c, HG_E_INVALID, "%s: mesh %d: index %d of triangle %lld is outside the %d vertices", who, mesh_index,
+                    indices[bad], static_cast<long long>(bad / 3), n_vertices);
+    if (int rc = set_device(c)) return rc;
+    const uint32_t key = c->dev_meshes[size_t(mesh_index)].tri_offset;
+    auto old = c->vertex_bindings.find(key);
+    if (old != c->vertex_bindings.end()) {  // a new list: the old one goes, and its skin with it
+        HG_HIP(c, hipStreamSynchronize(c->stream));
+        release_binding(old->second);
+        c->vertex_bindings.erase(old);
+    }
+    hg_ctx::VertexBinding b;
+    if (int rc = upload(c, b.indices, indices, size_t(n_tris) * 3 * sizeof(int32_t))) return rc;
+    HG_HIP(c, hipStreamSynchronize(c->stream));  // the caller's array is free again
+    b.n_tris = n_tris;
+    b.n_vertices = n_vertices;
+    c->vertex_bindings[key] = b;
+    return HG_OK;
+}
+
+int hg_deform_mesh_device(hg_ctx* c, int32_t mesh_index, const void* d_positions, const void* d_normals,
+                          int32_t n_vertices, int32_t how, int32_t leaf_size, float node_cost, void* d_order,
+                          uint64_t geometry_generation) {
+    static const char* who = "hg_deform_mesh_device";
+    if (!c) return HG_E_INVALID;
+    if (int rc = hg_ctx_flush(c)) return rc;
+    hg_ctx::VertexBinding* b = nullptr;
+    if (int rc = deform_check(c, who, mesh_index, d_positions, d_normals, n_vertices, how, b)) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_positions) & 3u) || (reinterpret_cast<uintptr_t>(d_normals) & 3u) ||
+        (reinterpret_cast<uintptr_t>(d_order) & 3u))
+        return fail(c, HG_E_INVALID, "%s: the position, normal and order arrays must be 4-byte aligned", who);
+    return deform_device(c, mesh_index, *b, d_positions, d_normals, how, leaf_size, node_cost, d_order, geometry_generation);
+}
+
+int hg_deform_mesh(hg_ctx* c, int32_t mesh_index, const float* positions, const float* normals, int32_t n_vertices,
+                   int32_t how, int32_t leaf_size, float node_cost, int32_t* order, uint64_t geometry_generation) {
+    static const char* who = "hg_deform_mesh";
+    if (!c) return HG_E_INVALID;
+    if (int rc = hg_ctx_flush(c)) return rc;
+    hg_ctx::VertexBinding* b = nullptr;
+    if (int rc = deform_check(c, who, mesh_index, positions, normals, n_vertices, how, b)) return rc;
+    const size_t bytes = size_t(n_vertices) * 3 * sizeof(float);
+    if (int rc = stage(c, c->deform_positions, positions, bytes)) return rc;
+    if (int rc = stage(c, c->deform_normals, normals, bytes)) return rc;
+    if (int rc = deform_device(c, mesh_index, *b, c->deform_positions.p, c->deform_normals.p, how, leaf_size, node_cost,
+                               nullptr, geometry_generation))
+        return rc;
+    return order_to_host(c, how, order, b->n_tris);
+}
+
+int hg_set_mesh_skin(hg_ctx* c, int32_t mesh_index, const float* rest_positions, const float* rest_normals,
+                     const uint16_t* bone_indices, const float* weights, int32_t n_vertices, int32_t n_bones) {
+    static const char* who = "hg_set_mesh_skin";
+    if (!c) return HG_E_INVALID;
+    if (int rc = hg_ctx_flush(c)) return rc;
+    hg_ctx::VertexBinding* b = nullptr;
+    if (int rc = binding_of(c, who, mesh_index, b)) return rc;
+    if (!rest_positions || !rest_normals || !bone_indices || !weights)
+        return fail(c, HG_E_INVALID, "%s: null rest pose, bone index or weight array", who);
+    if (n_vertices != b->n_vertices)
+        return fail(c, HG_E_INVALID, "%s: mesh %d: %d vertices, its binding holds %d", who, mesh_index, n_vertices,
+                    b->n_vertices);
+    if (n_bones < 1 || n_bones > 65536) return fail(c, HG_E_INVALID, "%s: n_bones %d outside 1..65536", who, n_bones);
+    const int64_t bad = hg_skin_first_bad_bone(bone_indices, n_vertices, n_bones);
+    if (bad >= 0)
+        return fail(c, HG_E_INVALID, "%s: mesh %d: bone index %d of vertex %lld is not below the %d bones", who, mesh_index,
+                    int(bone_indices[bad]), static_cast<long long>(bad / HG_SKIN_INFLUENCES), n_bones);
+    if (int rc = set_device(c)) return rc;
+    HG_HIP(c, hipStreamSynchronize(c->stream));  // (a reallocation frees the old arrays)
+    const size_t nv = size_t(n_vertices);
+    int rc;
+    if ((rc = upload(c, b->rest_positions, rest_positions, nv * 3 * sizeof(float)))) return rc;
+    if ((rc = upload(c, b->rest_normals, rest_normals, nv * 3 * sizeof(float)))) return rc;
+    if ((rc = upload(c, b->bone_indices, bone_indices, nv * HG_SKIN_INFLUENCES * sizeof(uint16_t)))) return rc;
+    if ((rc = upload(c, b->weights, weights, nv * HG_SKIN_INFLUENCES * sizeof(float)))) return rc;
+    if ((rc = ensure(c, b->positions, nv * 3 * sizeof(float)))) return rc;
+    if ((rc = ensure(c, b->normals, nv * 3 * sizeof(float)))) return rc;
+    HG_HIP(c, hipStreamSynchronize(c->stream));  // the caller's arrays are free again
+    b->n_bones = n_bones;
+    b->skinned = false;
+    return HG_OK;
+}
+
+int hg_skin_mesh_device(hg_ctx* c, int32_t mesh_index, const void* d_bones, int32_t n_bones, int32_t how,
+                        int32_t leaf_size, float node_cost, void* d_order, uint64_t geometry_generation) {
+    static const char* who = "hg_skin_mesh_device";
+    if (!c) return HG_E_INVALID;
+    if (int rc = hg_ctx_flush(c)) return rc;
+    hg_ctx::VertexBinding* b = nullptr;
+    if (int rc = skin_check(c, who, mesh_index, d_bones, n_bones, how, b)) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_bones) & 3u) || (reinterpret_cast<uintptr_t>(d_order) & 3u))
+        return fail(c, HG_E_INVALID, "%s: the bone and order arrays must be 4-byte aligned", who);
+    return skin_device(c, mesh_index, *b, d_bones, how, leaf_size, node_cost, d_order, geometry_generation);
+}
+
+int hg_skin_mesh(hg_ctx* c, int32_t mesh_index, const float* bones, int32_t n_bones, int32_t how, int32_t leaf_size,
+                 float node_cost, int32_t* order, uint64_t geometry_generation) {
+    static const char* who = "hg_skin_mesh";
+    if (!c) return HG_E_INVALID;
+    if (int rc = hg_ctx_flush(c)) return rc;
+    hg_ctx::VertexBinding* b = nullptr;
+    if (int rc = skin_check(c, who, mesh_index, bones, n_bones, how, b)) return rc;
+    if (int rc = stage(c, c->deform_bones, bones, size_t(n_bones) * HG_SKIN_BONE_FLOATS * sizeof(float))) return rc;
+    if (int rc = skin_device(c, mesh_index, *b, c->deform_bones.p, how, leaf_size, node_cost, nullptr, geometry_generation))
+        return rc;
+    return order_to_host(c, how, order, b->n_tris);
+}
+
+int hg_mesh_vertices_readback(hg_ctx* c, int32_t mesh_index, float* positions, float* normals, int32_t n_vertices) {
+    static const char* who = "hg_mesh_vertices_readback";
+    if (!c) return HG_E_INVALID;
+    if (int rc = hg_ctx_flush(c)) return rc;
+    hg_ctx::VertexBinding* b = nullptr;
+    if (int rc = binding_of(c, who, mesh_index, b)) return rc;
+    if (!b->skinned) return fail(c, HG_E_INVALID, "%s: mesh %d has not been skinned (hg_skin_mesh)", who, mesh_index);
+    if (n_vertices != b->n_vertices)
+        return fail(c, HG_E_INVALID, "%s: mesh %d: %d vertices, its binding holds %d", who, mesh_index, n_vertices,
+                    b->n_vertices);
+    if (int rc = set_device(c)) return rc;
+    HG_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = size_t(n_vertices) * 3 * sizeof(float);
+    if (positions) HG_HIP(c, hipMemcpy(positions, b->positions.p, bytes, hipMemcpyDeviceToHost));
+    if (normals) HG_HIP(c, hipMemcpy(normals, b->normals.p, bytes, hipMemcpyDeviceToHost));
+    return HG_OK;
+}
+
+}  // extern "C"

@@ -28,6 +28,7 @@
 #include "hg_host_pool.h"
 #include "hg_lbvh.h"
 #include "hg_refit.h"
+#include "hg_skin.h"
 
 namespace {
 
@@ -523,6 +524,21 @@ extern "C" int hg_pack_triangles(const float* V, const float* N, int32_t n_verti
         h.normalB = {N[3 * i1], N[3 * i1 + 1], N[3 * i1 + 2]};
         h.normalC = {N[3 * i2], N[3 * i2 + 1], N[3 * i2 + 2]};
     }
+    return HG_OK;
+}
+
+// hg_skin_vertices: the host twin of the device skin kernel (hg_deform.hip), over the contract of hg_skin.h.  Everything
+// is validated before the first vertex is written.
+extern "C" int hg_skin_vertices(const float* rest_positions, const float* rest_normals, const uint16_t* bone_indices,
+                                const float* weights, int32_t n_vertices, const float* bones, int32_t n_bones,
+                                float* out_positions, float* out_normals) {
+    if (!rest_positions || !rest_normals || !bone_indices || !weights || !bones || !out_positions || !out_normals)
+        return HG_E_INVALID;
+    if (n_vertices <= 0 || n_bones < 1 || n_bones > 65536) return HG_E_INVALID;
+    if (hg_skin_first_bad_bone(bone_indices, n_vertices, n_bones) >= 0) return HG_E_INVALID;
+    for (int64_t v = 0; v < n_vertices; ++v)
+        hg_skin_vertex(bones, bone_indices + 4 * v, weights + 4 * v, rest_positions + 3 * v, rest_normals + 3 * v,
+                       out_positions + 3 * v, out_normals + 3 * v);
     return HG_OK;
 }
 

@@ -374,6 +374,8 @@ int finish_device(hg_ctx* c, int32_t mesh_index, const std::vector<int32_t>& ins
     if (!tree.plan.records.empty())
         if ((rc = upload(c, tree.list, tree.plan.records.data(), tree.plan.records.size() * sizeof(uint32_t)))) return rc;
     if ((rc = refit_device(c, tree, instances, B.tris.p, n_tris, geometry_generation))) return rc;
+    // an index list bound to the tree (hg_set_mesh_vertices) follows the triangles into the new order
+    if ((rc = deform_follow_order(c, first.tri_offset, static_cast<const uint32_t*>(B.index_sorted.p), n))) return rc;
     // the traversal's stack: what a full upload of the scene with this tree sets (every mesh's tree has its plan cached:
     // refit_check walked the others)
     uint32_t max_depth = 0;

@@ -238,6 +238,13 @@ void refit_reset(hg_ctx* c) {
     for (auto& kv : c->refit_trees) release(kv.second.list);
     c->refit_trees.clear();
     c->rebuild_slots.clear();
+    for (auto& kv : c->vertex_bindings) {
+        hg_ctx::VertexBinding& b = kv.second;
+        for (DevBuf* d : {&b.indices, &b.spare, &b.rest_positions, &b.rest_normals, &b.bone_indices, &b.weights,
+                          &b.positions, &b.normals})
+            release(*d);
+    }
+    c->vertex_bindings.clear();
 }
 
 }  // namespace hgrt

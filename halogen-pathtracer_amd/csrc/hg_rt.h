@@ -1,5 +1,5 @@
 // hg_rt.h — what the runtime's translation units (hg_runtime.hip, hg_render.hip, hg_display.hip, hg_query.hip,
-// hg_denoise.hip, hg_refit.hip, hg_lbvh.hip, hg_comm.hip) share over a context: private to libhalogen_hip.so, none of it in the C-ABI.  The
+// hg_denoise.hip, hg_refit.hip, hg_lbvh.hip, hg_deform.hip, hg_comm.hip) share over a context: private to libhalogen_hip.so, none of it in the C-ABI.  The
 // helpers are in namespace hgrt (each is defined in the file named beside it); the hg_ctx_* functions are the
 // context's services to hg_comm.hip and to each other.
 #pragma once
@@ -87,5 +87,10 @@ int refit_check(hg_ctx* c, int32_t mesh_index, const void* tris, int32_t n_tris,
                 std::vector<int32_t>& instances);
 int refit_device(hg_ctx* c, hg_ctx::RefitTree& tree, const std::vector<int32_t>& instances, const void* d_tris,
                  int32_t n_tris, uint64_t geometry_generation);
+
+// ---- hg_deform.hip ----
+// After a rebuild of the tree at `tri_offset`: if an index list is bound to it (hg_set_mesh_vertices), permute it on the
+// context stream by the rebuild's order (d_order: n_tris uint32 on the device), so it stays in the tree's triangle order
+int deform_follow_order(hg_ctx* c, uint32_t tri_offset, const uint32_t* d_order, uint32_t n_tris);
 
 }  // namespace hgrt

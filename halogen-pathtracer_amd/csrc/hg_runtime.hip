@@ -255,7 +255,8 @@ void hg_destroy(hg_ctx* c) {
                       &c->guide1, &c->denoise_work[0], &c->denoise_work[1], &c->refit_in, &c->refit_raw, &c->lbvh.points,
                       &c->lbvh.partial, &c->lbvh.bounds, &c->lbvh.codes, &c->lbvh.index, &c->lbvh.codes_sorted,
                       &c->lbvh.index_sorted, &c->lbvh.sort_temp, &c->lbvh.tris, &c->lbvh.refs, &c->lbvh.topo,
-                      &c->lbvh.live, &c->lbvh.new_index, &c->lbvh.scan_temp})
+                      &c->lbvh.live, &c->lbvh.new_index, &c->lbvh.scan_temp, &c->deform_positions, &c->deform_normals,
+                      &c->deform_bones})
         release(*b);
     refit_reset(c);
     // The trace streams first, the server's stream after them: destroyed before them, the next hipStreamDestroy of a

@@ -216,5 +216,9 @@
 #define HG_STREAM_LDS_STACK 12  // the same for the streaming kernel (12 and 14 measured equal, 10 equal to 16 without the
                                 // mesh records in LDS; 12 leaves LDS room for 16 meshes, HG_WAVE_LDS_BUDGET)
 #endif
+#ifndef HG_SKIN_LDS_BONES
+#define HG_SKIN_LDS_BONES 256  // skin kernel (hg_deform.hip): a palette of at most this many bones sits in the workgroup's
+                               // LDS (12 KiB of 48-B bones beside 6 KiB of staging); a larger one is read from global memory
+#endif
 
 constexpr size_t kFrameColorCap = size_t(4) << 30;  // frame-parallel colour buffer cap (bytes)

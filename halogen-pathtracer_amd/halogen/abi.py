@@ -162,7 +162,13 @@ EXPORTS = [
     "hg_refit_blas", "hg_refit_mesh", "hg_refit_mesh_device", "hg_scene_readback",
     "hg_build_blas_lbvh", "hg_rebuild_mesh", "hg_rebuild_mesh_device",
     "hg_build_blas_lbvh_sah", "hg_rebuild_mesh_sah", "hg_rebuild_mesh_sah_device",
+    "hg_set_mesh_vertices", "hg_deform_mesh", "hg_deform_mesh_device", "hg_set_mesh_skin", "hg_skin_mesh",
+    "hg_skin_mesh_device", "hg_skin_vertices", "hg_mesh_vertices_readback",
 ]
+# hg_deform_mesh / hg_skin_mesh: what follows the pack (Context.deform_mesh(how=...))
+HG_DEFORM_REFIT, HG_DEFORM_REBUILD, HG_DEFORM_REBUILD_SAH = 0, 1, 2
+DEFORM_KINDS = {"refit": HG_DEFORM_REFIT, "lbvh": HG_DEFORM_REBUILD, "sah": HG_DEFORM_REBUILD_SAH}
+HG_SKIN_LDS_BONES = 256  # csrc/hg_tunables.h: the largest bone palette the skin kernel keeps in LDS
 # hg_scene_readback: the device scene's arrays (layouts private to the library, csrc/hg_layout.h)
 HG_SCENE_NODES, HG_SCENE_LEAVES, HG_SCENE_TRIS, HG_SCENE_NORMALS, HG_SCENE_MESHES = 0, 1, 2, 3, 4
 SCENE_ARRAYS = {"nodes": HG_SCENE_NODES, "leaves": HG_SCENE_LEAVES, "tris": HG_SCENE_TRIS,
@@ -249,6 +255,14 @@ def lib() -> C.CDLL:
         "hg_build_blas_lbvh_sah": (i64, [P, i32, C.c_float, i64, P, P, P, i64, f32p]),
         "hg_rebuild_mesh_sah": (C.c_int, [P, i32, P, i32, C.c_float, P, C.c_uint64]),
         "hg_rebuild_mesh_sah_device": (C.c_int, [P, i32, P, i32, C.c_float, P, C.c_uint64]),
+        "hg_set_mesh_vertices": (C.c_int, [P, i32, P, i32, i32]),
+        "hg_deform_mesh": (C.c_int, [P, i32, P, P, i32, i32, i32, C.c_float, P, C.c_uint64]),
+        "hg_deform_mesh_device": (C.c_int, [P, i32, P, P, i32, i32, i32, C.c_float, P, C.c_uint64]),
+        "hg_set_mesh_skin": (C.c_int, [P, i32, P, P, P, P, i32, i32]),
+        "hg_skin_mesh": (C.c_int, [P, i32, P, i32, i32, i32, C.c_float, P, C.c_uint64]),
+        "hg_skin_mesh_device": (C.c_int, [P, i32, P, i32, i32, i32, C.c_float, P, C.c_uint64]),
+        "hg_skin_vertices": (C.c_int, [P, P, P, P, i32, P, i32, P, P]),
+        "hg_mesh_vertices_readback": (C.c_int, [P, i32, P, P, i32]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -525,6 +539,126 @@ class Context:
                     name)
         return order
 
+    # --- deforming a mesh from its vertices (hg_set_mesh_vertices, hg_deform_mesh, hg_set_mesh_skin, hg_skin_mesh) ----
+    def set_mesh_vertices(self, mesh_index: int, indices, n_vertices: int) -> None:
+        """Bind the index list of mesh `mesh_index` ((n, 3) integers: its triangles in their current order, as they were
+        uploaded) to its tree on the device, for deform_mesh / skin_mesh.  The library keeps the list in step with every
+        later rebuild of the tree; the binding lives until the next full upload of the scene."""
+        idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
+        self._check(lib().hg_set_mesh_vertices(self._h, int(mesh_index), _ptr(idx) if idx.size else None, idx.shape[0],
+                                               int(n_vertices)), "hg_set_mesh_vertices")
+
+    def _device_floats(self, a, cols, what):
+        """`a` as (the array kept alive, pointer, rows, is_device): a contiguous (rows, cols) float32 torch tensor on the context's device
+        (its stream synchronised: the data is complete before the call), or anything numpy takes"""
+        if hasattr(a, "data_ptr") and not isinstance(a, np.ndarray):
+            import torch
+
+            if not (a.is_cuda and a.device.index == self.device and a.dtype == torch.float32 and a.dim() == 2 and
+                    a.shape[1] == cols and a.is_contiguous()):
+                raise ValueError(f"device {what} must be a contiguous (n, {cols}) float32 tensor on cuda:{self.device}")
+            return a, C.c_void_p(a.data_ptr()), a.shape[0], True
+        h = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, cols)
+        return h, (_ptr(h) if h.size else None), h.shape[0], False
+
+    def _n_bound_triangles(self, mesh_index: int) -> int:
+        """The triangles from the mesh's offset to the next mesh's (or the scene's end) in the device scene: room for a
+        rebuild's order, which is never longer (no other tree shares a rebuilt mesh's triangles)"""
+        m = self.scene_readback("meshes").view(np.uint32).reshape(-1, 36)
+        if not 0 <= int(mesh_index) < len(m):
+            return 0  # (the entry point refuses the index before it writes an order)
+        start = int(m[int(mesh_index), 17])
+        later = [int(o) for o in m[:, 17] if int(o) > start]
+        n = C.c_size_t(0)
+        self._check(lib().hg_scene_readback(self._h, HG_SCENE_TRIS, None, 0, C.byref(n)), "hg_scene_readback")
+        return (min(later) if later else n.value // 36) - start  # (the device keeps 9 floats a triangle)
+
+    def deform_mesh(self, mesh_index: int, positions, normals, how="refit", leaf_size: int = 0, node_cost: float = 0.0,
+                    generation: int = 0):
+        """Move mesh `mesh_index` (bound by set_mesh_vertices) to new vertex positions and normals, (n_vertices, 3) float32
+        each: the triangles are packed on the device from the bound index list, then the mesh's tree is refitted
+        (how="refit": refit_mesh), rebuilt as a linear BVH (how="lbvh", leaf_size: rebuild_mesh) or rebuilt with leaves
+        chosen by surface area (how="sah", node_cost: rebuild_mesh_sah).  Both arrays on the host (numpy), or both
+        contiguous float32 torch tensors on the context's device, read in place.  The rebuild kinds return the new
+        order as rebuild_mesh does (a torch int32 tensor for tensors, a numpy int32 array otherwise); "refit" returns
+        None."""
+        kind = DEFORM_KINDS[how] if isinstance(how, str) else int(how)
+        p, pp, n, dev = self._device_floats(positions, 3, "positions")
+        q, qp, nq, dev_q = self._device_floats(normals, 3, "normals")
+        if dev != dev_q or n != nq:
+            raise ValueError("positions and normals must both be numpy arrays or both device tensors, of one length")
+        order = order_ptr = None
+        if kind != HG_DEFORM_REFIT:
+            n_tris = self._n_bound_triangles(mesh_index)
+            if dev:
+                import torch
+
+                order = torch.empty(n_tris, dtype=torch.int32, device=p.device)
+                order_ptr = C.c_void_p(order.data_ptr())
+            else:
+                order = np.zeros(n_tris, dtype=np.int32)
+                order_ptr = _ptr(order)
+        if dev:
+            import torch
+
+            torch.cuda.current_stream(p.device).synchronize()  # the vertices are complete before the call
+        name = "hg_deform_mesh_device" if dev else "hg_deform_mesh"
+        self._check(getattr(lib(), name)(self._h, int(mesh_index), pp, qp, n, kind, int(leaf_size), float(node_cost),
+                                         order_ptr, int(generation)), name)
+        return order
+
+    def set_mesh_skin(self, mesh_index: int, rest_positions, rest_normals, bone_indices, weights, n_bones: int) -> None:
+        """Give a bound mesh its rest pose ((n_vertices, 3) positions and normals) and influences ((n_vertices, 4) bone
+        indices below n_bones and (n_vertices, 4) weights, used as given) for skin_mesh.  Host arrays."""
+        p = np.ascontiguousarray(rest_positions, dtype=np.float32).reshape(-1, 3)
+        q = np.ascontiguousarray(rest_normals, dtype=np.float32).reshape(-1, 3)
+        b = np.asarray(bone_indices)
+        if b.size and (b.min() < 0 or b.max() > 65535):
+            raise ValueError("bone indices must fit 16 bits")
+        b = np.ascontiguousarray(b, dtype=np.uint16).reshape(-1, 4)
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1, 4)
+        if not (len(p) == len(q) == len(b) == len(w)):
+            raise ValueError("rest positions, rest normals, bone indices and weights must hold one row per vertex")
+        self._check(lib().hg_set_mesh_skin(self._h, int(mesh_index), _ptr(p), _ptr(q), _ptr(b), _ptr(w), len(p),
+                                           int(n_bones)), "hg_set_mesh_skin")
+
+    def skin_mesh(self, mesh_index: int, bones, how="refit", leaf_size: int = 0, node_cost: float = 0.0,
+                  generation: int = 0):
+        """Pose a skinned mesh (set_mesh_skin) by a bone palette, (n_bones, 12) float32: row-major 3 x 4 matrices, on the
+        host or as a contiguous torch tensor on the context's device.  The vertices are skinned on the device
+        (linear blend, abi.skin_vertices' arithmetic bit for bit) and then go the way of deform_mesh; `how`, the other
+        arguments and the returned order are deform_mesh's."""
+        kind = DEFORM_KINDS[how] if isinstance(how, str) else int(how)
+        b, bp, n_bones, dev = self._device_floats(bones, 12, "bones")
+        order = order_ptr = None
+        if kind != HG_DEFORM_REFIT:
+            n_tris = self._n_bound_triangles(mesh_index)
+            if dev:
+                import torch
+
+                order = torch.empty(n_tris, dtype=torch.int32, device=b.device)
+                order_ptr = C.c_void_p(order.data_ptr())
+            else:
+                order = np.zeros(n_tris, dtype=np.int32)
+                order_ptr = _ptr(order)
+        if dev:
+            import torch
+
+            torch.cuda.current_stream(b.device).synchronize()  # the palette is complete before the call
+        name = "hg_skin_mesh_device" if dev else "hg_skin_mesh"
+        self._check(getattr(lib(), name)(self._h, int(mesh_index), bp, n_bones, kind, int(leaf_size), float(node_cost),
+                                         order_ptr, int(generation)), name)
+        return order
+
+    def mesh_vertices_readback(self, mesh_index: int, n_vertices: int) -> tuple[np.ndarray, np.ndarray]:
+        """A diagnostic copy of the vertices the last skin_mesh of the mesh produced: (n_vertices, 3) float32 positions
+        and normals."""
+        p = np.zeros((int(n_vertices), 3), dtype=np.float32)
+        q = np.zeros((int(n_vertices), 3), dtype=np.float32)
+        self._check(lib().hg_mesh_vertices_readback(self._h, int(mesh_index), _ptr(p), _ptr(q), int(n_vertices)),
+                    "hg_mesh_vertices_readback")
+        return p, q
+
     def scene_readback(self, which) -> np.ndarray:
         """A diagnostic copy of one array of the device scene ("nodes", "leaves", "tris", "normals", "meshes" or an
         HG_SCENE_* value) as bytes: two contexts hold the same scene exactly when all five are equal."""
@@ -697,6 +831,29 @@ def refit_blas(triangles, nodes) -> None:
     rc = lib().hg_refit_blas(_ptr(triangles), len(triangles), _ptr(nodes), len(nodes))
     if rc != HG_OK:
         raise HalogenError(f"hg_refit_blas failed ({rc}): a range, the depth or a cycle of the tree", rc)
+
+
+def skin_vertices(rest_positions, rest_normals, bone_indices, weights, bones):
+    """hg_skin_vertices, the host twin of Context.skin_mesh: linear-blend skinning of (n, 3) rest positions and normals
+    by (n, 4) bone indices and weights (used as given) over `bones`, (n_bones, 12) row-major 3 x 4 matrices.  Normals go
+    through the 3 x 3 block (rigid and uniformly scaled bones) and are normalised where their length is not zero.
+    Returns (positions, normals), (n, 3) float32 each.  Needs no GPU."""
+    p = np.ascontiguousarray(rest_positions, dtype=np.float32).reshape(-1, 3)
+    q = np.ascontiguousarray(rest_normals, dtype=np.float32).reshape(-1, 3)
+    bi = np.asarray(bone_indices)
+    if bi.size and (bi.min() < 0 or bi.max() > 65535):
+        raise HalogenError("hg_skin_vertices: bone indices must fit 16 bits", HG_E_INVALID)
+    bi = np.ascontiguousarray(bi, dtype=np.uint16).reshape(-1, 4)
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1, 4)
+    b = np.ascontiguousarray(bones, dtype=np.float32).reshape(-1, 12)
+    if not (len(p) == len(q) == len(bi) == len(w)):
+        raise ValueError("rest positions, rest normals, bone indices and weights must hold one row per vertex")
+    out_p, out_q = np.empty_like(p), np.empty_like(q)
+    rc = lib().hg_skin_vertices(_ptr(p), _ptr(q), _ptr(bi), _ptr(w), len(p), _ptr(b), len(b), _ptr(out_p), _ptr(out_q))
+    if rc != HG_OK:
+        raise HalogenError(f"hg_skin_vertices failed ({rc}): no vertices, no bones, or a bone index not below "
+                           f"{len(b)} bones", rc)
+    return out_p, out_q
 
 
 def build_blas_lbvh(triangles, leaf_size: int):

@@ -159,8 +159,13 @@ class DenoiseSettings:
 class HalogenRenderPass:
     """Progressive path tracing of a `halogen.scene.Scene` on one GPU (or one rank's tiles)."""
 
-    def __init__(self, settings: HalogenSettings, device: int = 0, context: abi.Context | None = None):
+    def __init__(self, settings: HalogenSettings, device: int = 0, context: abi.Context | None = None,
+                 vertex_deform: bool = False):
         self.settings = settings
+        # opt-in: after every full upload the pass binds each mesh's index list to the device (Context.set_mesh_vertices)
+        # and sends a deformed mesh's vertices and normals (24 B a vertex, packed on the device: Context.deform_mesh)
+        # where it otherwise sends the packed triangles (72 B a triangle: Context.refit_mesh).  The same device scene.
+        self.vertex_deform = bool(vertex_deform)
         self.s = clamp_settings(settings)
         self.ctx = context if context is not None else abi.Context(device)
         # the pass never reads the work counters (the reference has none); off, the render server may trace the next
@@ -219,6 +224,7 @@ class HalogenRenderPass:
     def UpdateObjectBuffers(self, scene):
         packed = scene.pack() if hasattr(scene, "pack") else scene
         generation = 0  # a bare PackedScene: every array compared
+        bind = False
         if hasattr(scene, "meshes") and hasattr(scene, "pack"):
             sig = tuple((m.cache_token, m.triangle_count, len(m.bvh)) for m in scene.meshes)
             serials = [m.deform_serial for m in scene.meshes]
@@ -227,6 +233,7 @@ class HalogenRenderPass:
             # order any more, so the scene is uploaded in full (pack() is always current)
             if sig != self._geometry[0] or any(r - r0 > 1 for r, r0 in zip(rebuilds, self._rebuild_serials)):
                 self._geometry = (sig, self._geometry[1] + 1)
+                bind = self.vertex_deform  # a full upload: the device's bindings go with it
             else:
                 # deformed meshes (RayTracingMesh.deform: moved vertices): where asked (rebuild=True) the mesh's tree is
                 # rebuilt on the device from the rebuild's own input, otherwise the triangles and BVH boxes are refitted
@@ -238,12 +245,16 @@ class HalogenRenderPass:
                         else:
                             self.ctx.rebuild_mesh(i, m.rebuild_input, m.rebuild_leaf, self._geometry[1])
                         if serials[i] != m.rebuild_at:
-                            self.ctx.refit_mesh(i, m.packed_triangles, self._geometry[1])
+                            self._refit(i, m)
                     elif serials[i] != self._deform_serials[i]:
-                        self.ctx.refit_mesh(i, m.packed_triangles, self._geometry[1])
+                        self._refit(i, m)
             self._deform_serials, self._rebuild_serials = serials, rebuilds
             generation = self._geometry[1]
         self.ctx.upload_scene(packed, generation)
+        if bind:
+            for i, m in enumerate(scene.meshes):
+                if m.triangle_count:
+                    self.ctx.set_mesh_vertices(i, m.triangles, len(m.vertices))
         self._guides_dirty = True
         self._scene_counts = (len(packed.spheres), len(packed.meshes))
         cube = self.settings.environmentCubemap
@@ -251,6 +262,14 @@ class HalogenRenderPass:
             self.ctx.upload_cubemap(cube.face_size, cube.n_mips, cube.texels)
             self._cubemap_uploaded = True
         return packed
+
+    def _refit(self, i, m):
+        """The device refit of a deformed mesh under the current generation: from its vertices (vertex_deform; a rebuild
+        on the device has kept the bound index list in the mesh's order) or from its packed triangles"""
+        if self.vertex_deform:
+            self.ctx.deform_mesh(i, m.vertices, m.normals, generation=self._geometry[1])
+        else:
+            self.ctx.refit_mesh(i, m.packed_triangles, self._geometry[1])
 
     # ---- RP:270-357 ----------------------------------------------------------------------------
     def Execute(self, scene, camera: Camera, n_frames: int = 1):

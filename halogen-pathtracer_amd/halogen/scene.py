@@ -235,6 +235,25 @@ class RayTracingMesh:
             abi.refit_blas(self.packed_triangles, self.bvh)
         self.deform_serial += 1
 
+    def set_skin(self, bone_indices, weights) -> None:
+        """Make the mesh skinnable: its current vertices and normals become the rest pose, with per vertex four bone
+        indices and four weights ((n_vertices, 4) each; the weights are used as given)."""
+        b = np.ascontiguousarray(bone_indices, dtype=np.uint16).reshape(-1, 4)
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1, 4)
+        if len(b) != len(self.vertices) or len(w) != len(self.vertices):
+            raise ValueError("set_skin takes four bone indices and four weights per vertex")
+        self.rest_vertices, self.rest_normals = self.vertices.copy(), self.normals.copy()
+        self.bone_indices, self.bone_weights = b, w
+
+    def pose(self, bones, rebuild=False, leaf_size: int = 0, node_cost: float = 0.0) -> None:
+        """Pose the skinned mesh (set_skin) by a bone palette, (n_bones, 12) row-major 3 x 4 matrices: the rest pose goes
+        through abi.skin_vertices (the host twin of Context.skin_mesh) and the result through deform() as it is, so the
+        host arrays stay current.  rebuild, leaf_size, node_cost: deform's."""
+        if getattr(self, "bone_indices", None) is None:
+            raise ValueError(f"{self.name}: pose needs set_skin")
+        v, n = abi.skin_vertices(self.rest_vertices, self.rest_normals, self.bone_indices, self.bone_weights, bones)
+        self.deform(v, n, rebuild=rebuild, leaf_size=leaf_size, node_cost=node_cost)
+
     @property
     def triangle_count(self) -> int:
         return len(self.triangles)

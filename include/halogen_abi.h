@@ -16,7 +16,7 @@
  *   plus what the reference never had: readback, counters, error text, multi-GPU tiling, ray queries, the denoised
  *   display, and deforming meshes (hg_refit_mesh: a device refit of one mesh's triangles and BVH boxes;
  *   hg_rebuild_mesh: a new tree for one mesh, built on the device in place; hg_rebuild_mesh_sah: the same with leaves
- *   chosen by surface area).
+ *   chosen by surface area; hg_deform_mesh / hg_skin_mesh: any of the three from a mesh's vertices or a bone palette).
  *
  * The host structs below are byte-identical to the reference's C# blittable structs
  * (RP:10-76, strides from Marshal.SizeOf at RP:163-167): a C# caller passes its List<T>.ToArray()
@@ -440,6 +440,73 @@ int hg_rebuild_mesh_sah(hg_ctx* ctx, int32_t mesh_index, const HalogenTriangle* 
                         float node_cost, int32_t* order, uint64_t geometry_generation);
 int hg_rebuild_mesh_sah_device(hg_ctx* ctx, int32_t mesh_index, const void* d_triangles, int32_t n_triangles,
                                float node_cost, void* d_order, uint64_t geometry_generation);
+
+/* ----------------------------------------------------------------------------------------------
+ * DEFORMING A MESH FROM ITS VERTICES: the front end of the three calls above for a caller who holds what a skinned
+ * character, cloth, a morph target or a simulation holds: vertex positions and normals (24 bytes a vertex) and a fixed
+ * index list, not 72-byte triangles in the tree's current order.  The library remembers the index list on the device,
+ * keeps it in step with every rebuild, packs the triangles there, and can produce the vertices itself by linear-blend
+ * skinning.  Everything after the pack is hg_refit_mesh_device / hg_rebuild_mesh_device / hg_rebuild_mesh_sah_device,
+ * unchanged.
+ *
+ * hg_set_mesh_vertices binds `indices` (3 * n_triangles, the mesh's triangles in its CURRENT order, as they sit in the
+ * uploaded triangle array; every index in [0, n_vertices)) to the tree of mesh `mesh_index`: to every instance of it,
+ * whichever instance later calls name.  The list is copied to the device (12 bytes a triangle).  After any successful
+ * hg_rebuild_mesh* or hg_rebuild_mesh_sah* of a bound tree, through the calls below or directly, the library permutes
+ * the bound list on the device by the rebuild's order, so the caller never touches it again; a tree without a binding
+ * takes exactly the path it took before.  The binding lives until the next FULL upload of the scene (a vouched, partial
+ * or skipped upload keeps it) or the next hg_set_mesh_vertices of the tree, which also drops its skin.
+ * Refused, with text and the scene untouched: everything hg_refit_mesh refuses; n_triangles other than the tree's
+ * triangle extent, or 0; n_vertices < 1; an index outside [0, n_vertices) (HG_E_INVALID).
+ *
+ * hg_deform_mesh / hg_deform_mesh_device take the mesh's moved vertices (`positions`, `normals`: 3 * n_vertices floats
+ * each; the device form: 4-byte aligned device memory on the context's device, complete before the call, `d_order`
+ * too), pack the bound indices and these vertices into a context-owned triangle buffer, byte for byte what
+ * hg_pack_triangles writes, and then do with that buffer exactly what, by `how`,
+ *   HG_DEFORM_REFIT        hg_refit_mesh_device,
+ *   HG_DEFORM_REBUILD      hg_rebuild_mesh_device (uses leaf_size) or
+ *   HG_DEFORM_REBUILD_SAH  hg_rebuild_mesh_sah_device (uses node_cost)
+ * does: flush, quiesce, guide images, accumulation, generation, upload rule, capacity, `order` and refusals are
+ * theirs.  Also refused (HG_E_INVALID): a mesh without a binding; n_vertices other than the bound count; a null
+ * position or normal array; an unknown `how`; a misaligned device pointer.  The normals are the caller's: recomputing
+ * vertex normals from the moved faces is out of scope, and so are morph-target blending (blend the vertices, then call
+ * this) and growing a tree's record capacity.
+ * The caller's duty afterwards is a refit's: its own host arrays must be current before any later full upload
+ * (hg_skin_vertices, hg_pack_triangles and hg_refit_blas or the rebuild twins give it that).
+ *
+ * hg_set_mesh_skin gives a bound mesh its rest pose and influences: per vertex a rest position and normal, four bone
+ * indices (uint16) and four weights.  Every bone index must be below n_bones (1..65536), checked on the host; refused
+ * (HG_E_INVALID, the scene and an earlier skin untouched) otherwise, for a mesh without a binding, a null array or
+ * n_vertices other than the bound count.
+ * hg_skin_mesh / hg_skin_mesh_device skin the rest pose by `bones` (n_bones, which must be the count the skin was set
+ * with; 12 floats each, a row-major 3 x 4 matrix; the device form: 4-byte aligned, complete before the call) into
+ * context-owned vertex buffers on the device, then follow the path of hg_deform_mesh_device from those.  The arithmetic
+ * is csrc/hg_skin.h's, bit for bit the host twin's: M = ((w0 B0 + w1 B1) + w2 B2) + w3 B3 per element with the weights
+ * as given, p' = M (p, 1), n' = normalize(M3x3 n) where its squared length is > 0: the 3 x 3 block, not its inverse
+ * transpose, which is right for rigid and uniformly scaled bones.  Dual-quaternion skinning is out of scope.
+ * hg_skin_vertices: the host twin (no device work).  Outputs must not alias inputs.  HG_E_INVALID, with nothing
+ * written: a null array, n_vertices < 1, n_bones outside 1..65536, a bone index not below n_bones.
+ * hg_mesh_vertices_readback: a diagnostic copy of the vertices the last hg_skin_mesh* of the mesh produced (either
+ * pointer may be NULL), in the spirit of hg_scene_readback.
+ * -------------------------------------------------------------------------------------------- */
+enum { HG_DEFORM_REFIT = 0, HG_DEFORM_REBUILD = 1, HG_DEFORM_REBUILD_SAH = 2 };
+int hg_set_mesh_vertices(hg_ctx* ctx, int32_t mesh_index, const int32_t* indices, int32_t n_triangles,
+                         int32_t n_vertices);
+int hg_deform_mesh(hg_ctx* ctx, int32_t mesh_index, const float* positions, const float* normals, int32_t n_vertices,
+                   int32_t how, int32_t leaf_size, float node_cost, int32_t* order, uint64_t geometry_generation);
+int hg_deform_mesh_device(hg_ctx* ctx, int32_t mesh_index, const void* d_positions, const void* d_normals,
+                          int32_t n_vertices, int32_t how, int32_t leaf_size, float node_cost, void* d_order,
+                          uint64_t geometry_generation);
+int hg_set_mesh_skin(hg_ctx* ctx, int32_t mesh_index, const float* rest_positions, const float* rest_normals,
+                     const uint16_t* bone_indices, const float* weights, int32_t n_vertices, int32_t n_bones);
+int hg_skin_mesh(hg_ctx* ctx, int32_t mesh_index, const float* bones, int32_t n_bones, int32_t how, int32_t leaf_size,
+                 float node_cost, int32_t* order, uint64_t geometry_generation);
+int hg_skin_mesh_device(hg_ctx* ctx, int32_t mesh_index, const void* d_bones, int32_t n_bones, int32_t how,
+                        int32_t leaf_size, float node_cost, void* d_order, uint64_t geometry_generation);
+int hg_skin_vertices(const float* rest_positions, const float* rest_normals, const uint16_t* bone_indices,
+                     const float* weights, int32_t n_vertices, const float* bones, int32_t n_bones,
+                     float* out_positions, float* out_normals);
+int hg_mesh_vertices_readback(hg_ctx* ctx, int32_t mesh_index, float* positions, float* normals, int32_t n_vertices);
 
 /* Environment cubemap (EnvironmentCubemap, HalgoenCompute.compute:48): RGBA32F texels, layout
  * [mip][face][y][x][4], faces +X,-X,+Y,-Y,+Z,-Z, mip m is max(1, face_size >> m) square.

@@ -1,0 +1,163 @@
+"""The host side of a deform from vertices: hg_skin_vertices (the twin of the device skin kernel, csrc/hg_skin.h) against
+a numpy restatement of the contract, bit for bit; what a rigid bone keeps; RayTracingMesh.set_skin / pose; refusals; the
+constants the Python layer mirrors; the host sanitizer program (make asan_skin).  The entry points that need a context
+are tests/test_gpu_deform.py's."""
+import ctypes as C
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import deform_cases as dc
+import refit_cases
+from halogen import abi
+
+ROOT = Path(__file__).resolve().parents[1]
+PKG = ROOT / "halogen-pathtracer_amd"
+f32 = np.float32
+
+
+def hard_case(n=10_007, n_bones=37, seed=11):
+    """~10^4 vertices under weights that do not sum to 1, zero and denormal weights, repeated bone indices; bones with
+    rotation, non-uniform scale and a translation of 1e6; a zero normal"""
+    rng = np.random.default_rng(seed)
+    p = rng.uniform(-10, 10, (n, 3)).astype(f32)
+    nrm = rng.normal(size=(n, 3))
+    nrm = (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(f32)
+    nrm[5] = 0.0
+    nrm[6] = [0.0, -0.0, 0.0]
+    idx = rng.integers(0, n_bones, (n, 4)).astype(np.uint16)
+    idx[::7] = idx[::7, :1]            # one bone four times
+    idx[1::7, 2] = idx[1::7, 0]        # ... and twice
+    idx[0] = n_bones - 1
+    w = rng.uniform(0, 1.5, (n, 4)).astype(f32)  # sums anywhere in (0, 6)
+    w[rng.uniform(size=w.shape) < 0.2] = 0.0
+    w[2::11, 1] = f32(1e-41)           # denormal weights
+    w[3::13] = 0.0                     # all four zero: the vertex collapses to the origin, its normal stays zero
+    w[4::17, 3] = f32(-0.25)
+    bones = []
+    for k in range(n_bones):
+        R = dc.rotation(rng.normal(size=3), rng.uniform(-np.pi, np.pi))
+        scale = rng.uniform(0.2, 3.0, 3) if k % 3 else (1.0, 1.0, 1.0)
+        t = rng.uniform(-5, 5, 3) if k % 5 else [1e6, -1e6, 1e6]
+        bones.append(dc.bone(R, t, scale))
+    return p, nrm, idx, w, np.stack(bones)
+
+
+def test_skin_vertices_equals_the_numpy_contract_bit_for_bit(built):
+    p, nrm, idx, w, bones = hard_case()
+    got_p, got_n = abi.skin_vertices(p, nrm, idx, w, bones)
+    want_p, want_n = dc.skin_numpy(p, nrm, idx, w, bones)
+    assert np.isfinite(want_p).all() and np.isfinite(want_n).all()
+    for got, want, what in ((got_p, want_p, "positions"), (got_n, want_n, "normals")):
+        bad = np.argwhere(dc.bits(got) != dc.bits(want))
+        assert bad.size == 0, (what, len(bad), bad[:4], got[bad[0][0]], want[bad[0][0]])
+    assert (dc.bits(got_n[5]) == 0).all(), "a zero normal stays as it is"
+    zero = ~w.any(axis=1)
+    assert zero.sum() > 100 and not got_p[zero].any() and not got_n[zero].any()
+    solid = (np.abs(w).sum(axis=1) > 0.1) & nrm.any(axis=1)  # (a matrix of denormals takes a normal to zero length)
+    lengths = np.linalg.norm(got_n[solid].astype(np.float64), axis=1)
+    assert np.abs(lengths - 1).max() < 4 * 2.0 ** -23
+
+
+def test_one_rigid_bone_keeps_unit_normals(built):
+    """A palette of one pure rotation: |n'| stays within a few ulp of 1 (the rotation's rounding is normalised away; what
+    is left is the rounding of d, of 1 / sqrt(d) and of the three products: under 4 ulp of 1), and positions keep their
+    distance from the origin to fp32 accuracy"""
+    rng = np.random.default_rng(3)
+    n = 4096
+    p = rng.uniform(-2, 2, (n, 3)).astype(f32)
+    nrm = rng.normal(size=(n, 3))
+    nrm = (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(f32)
+    idx = np.zeros((n, 4), np.uint16)
+    w = np.tile(f32([1, 0, 0, 0]), (n, 1))
+    bones = dc.bone(dc.rotation([1, 2, 3], 0.9)).reshape(1, 12)
+    out_p, out_n = abi.skin_vertices(p, nrm, idx, w, bones)
+    lengths = np.linalg.norm(out_n.astype(np.float64), axis=1)
+    assert np.abs(lengths - 1).max() <= 4 * 2.0 ** -23, np.abs(lengths - 1).max()
+    r0, r1 = np.linalg.norm(p.astype(np.float64), axis=1), np.linalg.norm(out_p.astype(np.float64), axis=1)
+    assert np.abs(r1 - r0).max() < 1e-5
+    want = nrm.astype(np.float64) @ dc.rotation([1, 2, 3], 0.9).T
+    assert np.abs(out_n - want).max() < 1e-6
+
+
+def test_pose_is_deform_of_the_skinned_vertices(built):
+    """RayTracingMesh.pose with a one-rotation palette = deform() of the vertices the contract gives: triangles and
+    boxes byte for byte, and the rest pose stays the rest pose over several poses"""
+    a = refit_cases.hazard_scene().meshes[3]
+    b = refit_cases.hazard_scene().meshes[3]
+    nv = len(a.vertices)
+    idx = np.zeros((nv, 4), np.uint16)
+    w = np.tile(f32([1, 0, 0, 0]), (nv, 1))
+    a.set_skin(idx, w)
+    rest_v, rest_n = a.vertices.copy(), a.normals.copy()
+    for angle in (0.4, -1.1):
+        bones = dc.bone(dc.rotation([0, 1, 0.2], angle), (0.1, 0.0, -0.2)).reshape(1, 12)
+        a.pose(bones)
+        v, n = dc.skin_numpy(rest_v, rest_n, idx, w, bones)
+        b.deform(v, n)
+        assert bytes(a.packed_triangles) == bytes(b.packed_triangles) and bytes(a.bvh) == bytes(b.bvh)
+        assert np.array_equal(a.vertices, v) and np.array_equal(a.normals, n)
+    assert a.deform_serial == 2
+    # the rebuild kinds pass through
+    idx4, w4 = dc.influences(nv, 4, seed=2)
+    a.set_skin(idx4, w4)
+    rest_v, rest_n = a.vertices.copy(), a.normals.copy()
+    bones = dc.rigid_palette(4, seed=5)
+    a.pose(bones, rebuild="sah")
+    b.deform(*dc.skin_numpy(rest_v, rest_n, idx4, w4, bones), rebuild="sah")
+    assert bytes(a.packed_triangles) == bytes(b.packed_triangles) and bytes(a.bvh) == bytes(b.bvh)
+    assert np.array_equal(a.triangles, b.triangles) and a.rebuild_serial == 1
+    with pytest.raises(ValueError):
+        refit_cases.hazard_scene().meshes[0].pose(bones)  # no set_skin
+    with pytest.raises(ValueError):
+        a.set_skin(idx4[:-1], w4[:-1])
+
+
+def test_skin_vertices_refusals(built):
+    p, nrm, idx, w, bones = hard_case(n=64, n_bones=5)
+    bad = idx.copy()
+    bad[17, 2] = 5  # = n_bones
+    with pytest.raises(abi.HalogenError) as e:
+        abi.skin_vertices(p, nrm, bad, w, bones)
+    assert e.value.rc == abi.HG_E_INVALID
+    with pytest.raises(abi.HalogenError) as e:  # n_vertices 0
+        abi.skin_vertices(p[:0], nrm[:0], idx[:0], w[:0], bones)
+    assert e.value.rc == abi.HG_E_INVALID
+    with pytest.raises(abi.HalogenError):  # no bones
+        abi.skin_vertices(p, nrm, np.zeros_like(idx), w, bones[:0])
+    with pytest.raises(abi.HalogenError):
+        abi.skin_vertices(p, nrm, idx.astype(np.int64) + 70000, w, bones)
+    L = abi.lib()
+    out_p, out_n = np.full_like(p, 7), np.full_like(nrm, 7)
+    args = [p, nrm, idx, w, len(p), bones, len(bones), out_p, out_n]
+    for k in (0, 1, 2, 3, 5, 7, 8):  # each array null in turn
+        a = [x.ctypes.data if isinstance(x, np.ndarray) else x for x in args]
+        a[k] = None
+        assert L.hg_skin_vertices(*a) == abi.HG_E_INVALID, k
+    a = [x.ctypes.data if isinstance(x, np.ndarray) else x for x in args]
+    a[2] = bad.ctypes.data
+    assert L.hg_skin_vertices(*a) == abi.HG_E_INVALID
+    assert (out_p == 7).all() and (out_n == 7).all(), "nothing is written on a refusal"
+    a[2] = idx.ctypes.data
+    assert L.hg_skin_vertices(*a) == abi.HG_OK and not (out_p == 7).all()
+
+
+def test_python_constants_match_the_sources(built):
+    tun = (PKG / "csrc" / "hg_tunables.h").read_text()
+    assert int(re.search(r"#define HG_SKIN_LDS_BONES (\d+)", tun).group(1)) == abi.HG_SKIN_LDS_BONES
+    header = (ROOT / "include" / "halogen_abi.h").read_text()
+    for name in ("HG_DEFORM_REFIT", "HG_DEFORM_REBUILD", "HG_DEFORM_REBUILD_SAH"):
+        assert int(re.search(r"\b%s = (\d+)" % name, header).group(1)) == getattr(abi, name)
+    assert sorted(abi.DEFORM_KINDS.values()) == [0, 1, 2]
+    assert abi.lib().hg_abi_version() == 6
+
+
+def test_asan_skin_program():
+    """host/asan_skin.cpp under AddressSanitizer + UBSan: hg_skin_vertices and the checks of a binding's lists on random
+    and edge input (make asan_skin; a stand-alone program, host code only)."""
+    subprocess.run(["make", "-s", "-C", str(PKG), "asan_skin"], check=True)
+    r = subprocess.run([str(PKG / "build" / "asan_skin")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "asan_skin ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
