@@ -1,5 +1,6 @@
 // hg_ctx.h — the context object behind the C-ABI's opaque hg_ctx (private to libhalogen_hip.so; the functions over it
-// that its translation units share are declared in hg_rt.h).
+// that its translation units share are declared in hg_rt.h).  What of it is host logic with a header of its own, tested
+// on the CPU: the tree bookkeeping of the mesh updates (hg_mesh_trees.h), the display slot ring (hg_slot_ring.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,8 +11,7 @@
 #include <vector>
 
 #include "halogen_abi.h"
-#include "hg_layout.h"
-#include "hg_refit_plan.h"
+#include "hg_mesh_trees.h"
 #include "hg_slot_ring.h"
 
 struct DevBuf {  // a device allocation owned by a context
@@ -27,7 +27,7 @@ struct hg_ctx {
     // scene
     bool has_scene = false;
     DevBuf spheres, meshes, materials, nodes, leaves, tris, normals;
-    int32_t n_spheres = 0, n_meshes = 0, n_materials = 0, n_tris = 0, n_nodes = 0;
+    int32_t n_spheres = 0, n_meshes = 0, n_materials = 0, n_nodes = 0;  // (the triangle count: trees.n_tris)
     uint32_t stack_depth = 2;
     // the caller's arrays of the last upload (spheres, meshes, materials, triangles, BVH entries), byte for byte: an
     // identical re-upload (the reference re-uploads on every camera move) is detected and skipped
@@ -35,29 +35,23 @@ struct hg_ctx {
     std::vector<HgDevMesh> dev_meshes;  // the device mesh table of the last upload (partial re-uploads start from it)
     uint64_t scene_uploads = 0, scene_uploads_skipped = 0, scene_uploads_partial = 0, scene_uploads_vouched = 0;
     uint64_t geometry_gen = 0;  // hg_upload_scene_gen: the caller's geometry generation of the last upload (0: none)
-    // Refit (hg_refit_mesh, hg_refit.hip).  Host copies of what the device scene's topology is read from, kept by every
-    // full upload: the two refs of each node record, the leaf table, the bytes of the four geometry arrays; and the local
-    // boxes of each mesh root's two children (a refit replaces its meshes').  geometry_stale: a refit changed the device
-    // since the last full upload, so scene_copy[3] and [4] no longer describe it (hg_upload_decide_refit).  Per refitted
-    // tree (root ref << 32 | triangle offset) its plan on the device, until the next full upload.
-    std::vector<uint32_t> rec_refs, leaf_table;
+    // Mesh updates (hg_refit_mesh, hg_rebuild_mesh[_sah], hg_deform_mesh, hg_skin_mesh: one path, update_mesh of
+    // hg_refit.hip).  `trees` is the host's picture of the device scene's topology, kept by every full upload and by
+    // every rebuild, with every check an update makes against it (hg_mesh_trees.h); refit_lists holds, per tree under
+    // trees' key, its plan's records on the device once a refit used them (a rebuild hands the list on to the new tree).
+    // Beside them: the bytes of the four geometry arrays and the local boxes of each mesh root's two children (a refit
+    // replaces its meshes').  geometry_stale: an update changed the device since the last full upload, so scene_copy[3]
+    // and [4] no longer describe it (hg_upload_decide_refit).
+    HgMeshTrees trees;
+    std::map<uint64_t, DevBuf> refit_lists;
     size_t geometry_bytes[4] = {};  // nodes, leaves, triangles, normals as uploaded (the buffers hold at least 16 B)
     std::vector<HgRootPair> root_pairs;
     bool geometry_stale = false;
-    struct RefitTree {
-        HgRefitPlan plan;
-        DevBuf list;  // plan.records
-    };
-    std::map<uint64_t, RefitTree> refit_trees;
-    DevBuf refit_in, refit_raw;  // the host-pointer form's triangles; one raw box (6 floats) per record of a tree
+    // the triangles of an update on the device where the caller's are not (staged from the host, or packed from
+    // vertices); one raw box (6 floats) per record of a tree
+    DevBuf refit_in, refit_raw;
     uint64_t scene_refits = 0;
-    // Rebuild (hg_rebuild_mesh, hg_lbvh.hip).  Per rebuilt tree, by its triangle offset (the root ref changes with the
-    // tree): the first record and the record span of the tree at the last full upload, which is its capacity from then
-    // on (a rebuild may leave the tree with fewer records, or with none).  The build's device scratch, grown on demand.
-    struct RebuildSlot {
-        uint32_t rec_min = 0, capacity = 0;
-    };
-    std::map<uint32_t, RebuildSlot> rebuild_slots;
+    // The rebuilds' device scratch (hg_lbvh.hip), grown on demand
     struct Lbvh {
         DevBuf points, partial, bounds;       // key points (3 floats each); per-workgroup and final pmin / pmax
         DevBuf codes, index, codes_sorted, index_sorted, sort_temp;
@@ -67,7 +61,7 @@ struct hg_ctx {
     } lbvh;
     uint64_t scene_rebuilds = 0;
     // Deform from vertices (hg_set_mesh_vertices, hg_deform_mesh, hg_skin_mesh; hg_deform.hip).  Per bound tree, by its
-    // triangle offset like rebuild_slots, until the next full upload: the mesh's index list on the device in the tree's
+    // triangle offset like trees.slots, until the next full upload: the mesh's index list on the device in the tree's
     // current triangle order (every rebuild of the tree permutes it into `spare` and swaps the two), and, once
     // hg_set_mesh_skin gave them, the rest pose, the influences and the vertices the last hg_skin_mesh* produced.
     struct VertexBinding {

@@ -1,11 +1,13 @@
 // hg_deform.hip — deforming geometry from where its users hold it, the vertices: hg_set_mesh_vertices binds a mesh's index
 // list to its tree on the device, hg_deform_mesh / hg_deform_mesh_device pack the 72-byte triangles from vertex arrays
 // there, hg_set_mesh_skin / hg_skin_mesh / hg_skin_mesh_device produce those vertices by linear-blend skinning (the
-// contract: hg_skin.h; the host twin: hg_skin_vertices, hg_host.cpp).  What follows the pack is hg_refit_mesh_device,
-// hg_rebuild_mesh_device or hg_rebuild_mesh_sah_device on the packed triangles, unchanged.  Not in the reference.
+// contract: hg_skin.h; the host twin: hg_skin_vertices, hg_host.cpp).  The deform and skin entry points fill a MeshUpdate
+// whose source is vertices or a palette; update_mesh (hg_refit.hip) takes from here the checks of that source
+// (vertex_source_check, before the tree's checks and before anything is launched) and the source as packed triangles
+// (vertex_source_device, after the quiesce), and goes on as for any other triangles.  Not in the reference.
 //
 // Three kernels, all on the context stream and ordered by it alone: no atomics, no kernel that waits on another
-// workgroup.  The kernels first, then the entry points of the C-ABI.
+// workgroup.  The kernels first, then the two halves of a vertex source, then the entry points of the C-ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,12 +19,9 @@
 
 using namespace hgrt;
 
-static_assert(sizeof(HalogenTriangle) == 72, "the pack kernel writes a triangle as 18 floats");
-
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kTriWords = 18;  // floats of a HalogenTriangle
 
 // Pack: out[t] = the HalogenTriangle of indices[3t .. 3t + 2], byte for byte what hg_pack_triangles writes.  A workgroup
 // takes 256 triangles: its 768 indices are read by consecutive lanes, a lane per corner; each corner's position and
@@ -120,12 +119,6 @@ __global__ __launch_bounds__(kBlock) void hg_deform_permute(const int32_t* __res
     d[2] = c2;
 }
 
-void release_binding(hg_ctx::VertexBinding& b) {
-    for (DevBuf* d : {&b.indices, &b.spare, &b.rest_positions, &b.rest_normals, &b.bone_indices, &b.weights, &b.positions,
-                      &b.normals})
-        release(*d);
-}
-
 // The scene, the mesh and its binding, for the entry point `who`
 int binding_of(hg_ctx* c, const char* who, int32_t mesh_index, hg_ctx::VertexBinding*& b) {
     if (!c->has_scene) return fail(c, HG_E_NOSCENE, "%s: hg_upload_scene not called", who);
@@ -139,91 +132,83 @@ int binding_of(hg_ctx* c, const char* who, int32_t mesh_index, hg_ctx::VertexBin
     return HG_OK;
 }
 
-// What hg_deform_mesh* check beyond the binding, before the first launch
-int deform_check(hg_ctx* c, const char* who, int32_t mesh_index, const void* positions, const void* normals,
-                 int32_t n_vertices, int32_t how, hg_ctx::VertexBinding*& b) {
-    if (int rc = binding_of(c, who, mesh_index, b)) return rc;
-    if (!positions || !normals) return fail(c, HG_E_INVALID, "%s: null position or normal array", who);
-    if (n_vertices != b->n_vertices)
-        return fail(c, HG_E_INVALID, "%s: mesh %d: %d vertices, its binding holds %d", who, mesh_index, n_vertices,
-                    b->n_vertices);
-    if (how != HG_DEFORM_REFIT && how != HG_DEFORM_REBUILD && how != HG_DEFORM_REBUILD_SAH)
-        return fail(c, HG_E_INVALID, "%s: unknown kind of deform %d", who, how);
-    return HG_OK;
-}
-
-// The pack into the context's triangle buffer, then the refit or rebuild of the mesh from it: the device entry point
-// itself, with its own checks, flush (nothing is held any more), quiesce and bookkeeping.  d_positions, d_normals:
-// n_vertices * 3 floats on the device, 4-byte aligned, complete.  A rebuild leaves its order in c->lbvh.index_sorted.
-int deform_device(hg_ctx* c, int32_t mesh_index, const hg_ctx::VertexBinding& b, const void* d_positions,
-                  const void* d_normals, int32_t how, int32_t leaf_size, float node_cost, void* d_order,
-                  uint64_t geometry_generation) {
-    const int32_t n_tris = b.n_tris;
-    if (int rc = set_device(c)) return rc;
-    if (int rc = ensure(c, c->refit_in, size_t(n_tris) * sizeof(HalogenTriangle))) return rc;
-    hipLaunchKernelGGL(hg_deform_pack, dim3(uint32_t((n_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                       static_cast<const int32_t*>(b.indices.p), uint32_t(n_tris), static_cast<const float*>(d_positions),
-                       static_cast<const float*>(d_normals), static_cast<float*>(c->refit_in.p));
-    HG_HIP(c, hipGetLastError());
-    if (how == HG_DEFORM_REBUILD)
-        return hg_rebuild_mesh_device(c, mesh_index, c->refit_in.p, n_tris, leaf_size, d_order, geometry_generation);
-    if (how == HG_DEFORM_REBUILD_SAH)
-        return hg_rebuild_mesh_sah_device(c, mesh_index, c->refit_in.p, n_tris, node_cost, d_order, geometry_generation);
-    return hg_refit_mesh_device(c, mesh_index, c->refit_in.p, n_tris, geometry_generation);
-}
-
-// A host array to a context-owned device buffer, on the context stream
-int stage(hg_ctx* c, DevBuf& buf, const void* src, size_t bytes) {
-    if (int rc = set_device(c)) return rc;
+// `bytes` of a host or device array into a context-owned device buffer, or the device array itself
+int on_device(hg_ctx* c, const MeshUpdate& u, const void* src, DevBuf& buf, size_t bytes, const void*& d) {
+    d = src;
+    if (u.device) return HG_OK;
     if (int rc = ensure(c, buf, bytes)) return rc;
     HG_HIP(c, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+    d = buf.p;
     return HG_OK;
-}
-
-int order_to_host(hg_ctx* c, int32_t how, int32_t* order, int32_t n_tris) {
-    if (order && how != HG_DEFORM_REFIT)
-        HG_HIP(c, hipMemcpy(order, c->lbvh.index_sorted.p, size_t(n_tris) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return HG_OK;
-}
-
-// What hg_skin_mesh* check before the first launch
-int skin_check(hg_ctx* c, const char* who, int32_t mesh_index, const void* bones, int32_t n_bones, int32_t how,
-               hg_ctx::VertexBinding*& b) {
-    if (int rc = binding_of(c, who, mesh_index, b)) return rc;
-    if (b->n_bones == 0) return fail(c, HG_E_INVALID, "%s: mesh %d has no skin (hg_set_mesh_skin)", who, mesh_index);
-    if (!bones) return fail(c, HG_E_INVALID, "%s: null bone palette", who);
-    if (n_bones != b->n_bones)
-        return fail(c, HG_E_INVALID, "%s: mesh %d: %d bones, its skin was bound with %d", who, mesh_index, n_bones, b->n_bones);
-    if (how != HG_DEFORM_REFIT && how != HG_DEFORM_REBUILD && how != HG_DEFORM_REBUILD_SAH)
-        return fail(c, HG_E_INVALID, "%s: unknown kind of deform %d", who, how);
-    return HG_OK;
-}
-
-// The skin kernel into the binding's vertex buffers, then the path of hg_deform_mesh_device from them
-int skin_device(hg_ctx* c, int32_t mesh_index, hg_ctx::VertexBinding& b, const void* d_bones, int32_t how,
-                int32_t leaf_size, float node_cost, void* d_order, uint64_t geometry_generation) {
-    if (int rc = set_device(c)) return rc;
-    const uint32_t nv = uint32_t(b.n_vertices);
-    const dim3 grid((nv + kBlock - 1) / kBlock);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, c->stream, static_cast<const float*>(b.rest_positions.p),
-                           static_cast<const float*>(b.rest_normals.p), static_cast<const uint2*>(b.bone_indices.p),
-                           static_cast<const float4*>(b.weights.p), nv, static_cast<const float*>(d_bones),
-                           uint32_t(b.n_bones), static_cast<float*>(b.positions.p), static_cast<float*>(b.normals.p));
-    };
-    if (b.n_bones <= HG_SKIN_LDS_BONES)
-        launch(hg_deform_skin<true>);
-    else
-        launch(hg_deform_skin<false>);
-    HG_HIP(c, hipGetLastError());
-    b.skinned = true;
-    return deform_device(c, mesh_index, b, b.positions.p, b.normals.p, how, leaf_size, node_cost, d_order,
-                         geometry_generation);
 }
 
 }  // namespace
 
 namespace hgrt {
+
+void release_binding(hg_ctx::VertexBinding& b) {
+    for (DevBuf* d : {&b.indices, &b.spare, &b.rest_positions, &b.rest_normals, &b.bone_indices, &b.weights, &b.positions,
+                      &b.normals})
+        release(*d);
+}
+
+// What an update from vertices or from a bone palette checks of its source, before the tree's checks: the binding,
+// the skin, the arrays and their counts, the kind
+int vertex_source_check(hg_ctx* c, const MeshUpdate& u, hg_ctx::VertexBinding*& b) {
+    if (int rc = binding_of(c, u.who, u.mesh_index, b)) return rc;
+    if (u.source == MeshUpdate::kBones) {
+        if (b->n_bones == 0) return fail(c, HG_E_INVALID, "%s: mesh %d has no skin (hg_set_mesh_skin)", u.who, u.mesh_index);
+        if (!u.a) return fail(c, HG_E_INVALID, "%s: null bone palette", u.who);
+        if (u.count != b->n_bones)
+            return fail(c, HG_E_INVALID, "%s: mesh %d: %d bones, its skin was bound with %d", u.who, u.mesh_index, u.count,
+                        b->n_bones);
+    } else {
+        if (!u.a || !u.b) return fail(c, HG_E_INVALID, "%s: null position or normal array", u.who);
+        if (u.count != b->n_vertices)
+            return fail(c, HG_E_INVALID, "%s: mesh %d: %d vertices, its binding holds %d", u.who, u.mesh_index, u.count,
+                        b->n_vertices);
+    }
+    if (u.how != HG_DEFORM_REFIT && u.how != HG_DEFORM_REBUILD && u.how != HG_DEFORM_REBUILD_SAH)
+        return fail(c, HG_E_INVALID, "%s: unknown kind of deform %d", u.who, u.how);
+    return HG_OK;
+}
+
+// The source of such an update as b.n_tris triangles in c->refit_in (large enough), on the context stream: a palette
+// through the skin kernel into the binding's vertex buffers, vertices (the caller's, or those) through the pack kernel
+int vertex_source_device(hg_ctx* c, const MeshUpdate& u, hg_ctx::VertexBinding& b) {
+    const void* d_positions = nullptr;
+    const void* d_normals = nullptr;
+    if (u.source == MeshUpdate::kBones) {
+        const void* d_bones = nullptr;
+        if (int rc = on_device(c, u, u.a, c->deform_bones, size_t(u.count) * HG_SKIN_BONE_FLOATS * sizeof(float), d_bones))
+            return rc;
+        const uint32_t nv = uint32_t(b.n_vertices);
+        const dim3 grid((nv + kBlock - 1) / kBlock);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, c->stream, static_cast<const float*>(b.rest_positions.p),
+                               static_cast<const float*>(b.rest_normals.p), static_cast<const uint2*>(b.bone_indices.p),
+                               static_cast<const float4*>(b.weights.p), nv, static_cast<const float*>(d_bones),
+                               uint32_t(b.n_bones), static_cast<float*>(b.positions.p), static_cast<float*>(b.normals.p));
+        };
+        if (b.n_bones <= HG_SKIN_LDS_BONES)
+            launch(hg_deform_skin<true>);
+        else
+            launch(hg_deform_skin<false>);
+        HG_HIP(c, hipGetLastError());
+        b.skinned = true;
+        d_positions = b.positions.p;
+        d_normals = b.normals.p;
+    } else {
+        const size_t bytes = size_t(u.count) * 3 * sizeof(float);
+        if (int rc = on_device(c, u, u.a, c->deform_positions, bytes, d_positions)) return rc;
+        if (int rc = on_device(c, u, u.b, c->deform_normals, bytes, d_normals)) return rc;
+    }
+    hipLaunchKernelGGL(hg_deform_pack, dim3(uint32_t((b.n_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                       static_cast<const int32_t*>(b.indices.p), uint32_t(b.n_tris), static_cast<const float*>(d_positions),
+                       static_cast<const float*>(d_normals), static_cast<float*>(c->refit_in.p));
+    HG_HIP(c, hipGetLastError());
+    return HG_OK;
+}
 
 int deform_follow_order(hg_ctx* c, uint32_t tri_offset, const uint32_t* d_order, uint32_t n_tris) {
     auto it = c->vertex_bindings.find(tri_offset);
@@ -248,12 +233,13 @@ int hg_set_mesh_vertices(hg_ctx* c, int32_t mesh_index, const int32_t* indices, 
     if (!c) return HG_E_INVALID;
     if (int rc = hg_ctx_flush(c)) return rc;
     if (c->has_scene && !indices) return fail(c, HG_E_INVALID, "%s: null index array", who);
-    hg_ctx::RefitTree* tree = nullptr;
+    const HgRefitPlan* plan = nullptr;
     std::vector<int32_t> instances;
-    if (int rc = refit_check(c, mesh_index, indices, n_tris, tree, instances)) return rc;
-    if (n_tris == 0 || uint32_t(n_tris) != tree->plan.extent)
-        return fail(c, HG_E_INVALID, "%s: mesh %d: %d triangles, its tree holds %u", who, mesh_index, n_tris,
-                    tree->plan.extent);
+    HgPackError err;
+    if (c->trees.check_refit(c->has_scene, c->dev_meshes, mesh_index, indices != nullptr, n_tris, plan, instances, err))
+        return fail(c, err);
+    if (n_tris == 0 || uint32_t(n_tris) != plan->extent)
+        return fail(c, HG_E_INVALID, "%s: mesh %d: %d triangles, its tree holds %u", who, mesh_index, n_tris, plan->extent);
     if (n_vertices <= 0) return fail(c, HG_E_INVALID, "%s: mesh %d: %d vertices", who, mesh_index, n_vertices);
     const int64_t bad = hg_skin_first_bad_index(indices, n_tris, n_vertices);
     if (bad >= 0)
@@ -279,31 +265,14 @@ int hg_set_mesh_vertices(hg_ctx* c, int32_t mesh_index, const int32_t* indices, 
 int hg_deform_mesh_device(hg_ctx* c, int32_t mesh_index, const void* d_positions, const void* d_normals,
                           int32_t n_vertices, int32_t how, int32_t leaf_size, float node_cost, void* d_order,
                           uint64_t geometry_generation) {
-    static const char* who = "hg_deform_mesh_device";
-    if (!c) return HG_E_INVALID;
-    if (int rc = hg_ctx_flush(c)) return rc;
-    hg_ctx::VertexBinding* b = nullptr;
-    if (int rc = deform_check(c, who, mesh_index, d_positions, d_normals, n_vertices, how, b)) return rc;
-    if ((reinterpret_cast<uintptr_t>(d_positions) & 3u) || (reinterpret_cast<uintptr_t>(d_normals) & 3u) ||
-        (reinterpret_cast<uintptr_t>(d_order) & 3u))
-        return fail(c, HG_E_INVALID, "%s: the position, normal and order arrays must be 4-byte aligned", who);
-    return deform_device(c, mesh_index, *b, d_positions, d_normals, how, leaf_size, node_cost, d_order, geometry_generation);
+    return update_mesh(c, {"hg_deform_mesh_device", mesh_index, MeshUpdate::kVertices, d_positions, d_normals, n_vertices,
+                           true, how, leaf_size, node_cost, d_order, geometry_generation});
 }
 
 int hg_deform_mesh(hg_ctx* c, int32_t mesh_index, const float* positions, const float* normals, int32_t n_vertices,
                    int32_t how, int32_t leaf_size, float node_cost, int32_t* order, uint64_t geometry_generation) {
-    static const char* who = "hg_deform_mesh";
-    if (!c) return HG_E_INVALID;
-    if (int rc = hg_ctx_flush(c)) return rc;
-    hg_ctx::VertexBinding* b = nullptr;
-    if (int rc = deform_check(c, who, mesh_index, positions, normals, n_vertices, how, b)) return rc;
-    const size_t bytes = size_t(n_vertices) * 3 * sizeof(float);
-    if (int rc = stage(c, c->deform_positions, positions, bytes)) return rc;
-    if (int rc = stage(c, c->deform_normals, normals, bytes)) return rc;
-    if (int rc = deform_device(c, mesh_index, *b, c->deform_positions.p, c->deform_normals.p, how, leaf_size, node_cost,
-                               nullptr, geometry_generation))
-        return rc;
-    return order_to_host(c, how, order, b->n_tris);
+    return update_mesh(c, {"hg_deform_mesh", mesh_index, MeshUpdate::kVertices, positions, normals, n_vertices, false, how,
+                           leaf_size, node_cost, order, geometry_generation});
 }
 
 int hg_set_mesh_skin(hg_ctx* c, int32_t mesh_index, const float* rest_positions, const float* rest_normals,
@@ -341,27 +310,14 @@ int hg_set_mesh_skin(hg_ctx* c, int32_t mesh_index, const float* rest_positions,
 
 int hg_skin_mesh_device(hg_ctx* c, int32_t mesh_index, const void* d_bones, int32_t n_bones, int32_t how,
                         int32_t leaf_size, float node_cost, void* d_order, uint64_t geometry_generation) {
-    static const char* who = "hg_skin_mesh_device";
-    if (!c) return HG_E_INVALID;
-    if (int rc = hg_ctx_flush(c)) return rc;
-    hg_ctx::VertexBinding* b = nullptr;
-    if (int rc = skin_check(c, who, mesh_index, d_bones, n_bones, how, b)) return rc;
-    if ((reinterpret_cast<uintptr_t>(d_bones) & 3u) || (reinterpret_cast<uintptr_t>(d_order) & 3u))
-        return fail(c, HG_E_INVALID, "%s: the bone and order arrays must be 4-byte aligned", who);
-    return skin_device(c, mesh_index, *b, d_bones, how, leaf_size, node_cost, d_order, geometry_generation);
+    return update_mesh(c, {"hg_skin_mesh_device", mesh_index, MeshUpdate::kBones, d_bones, nullptr, n_bones, true, how,
+                           leaf_size, node_cost, d_order, geometry_generation});
 }
 
 int hg_skin_mesh(hg_ctx* c, int32_t mesh_index, const float* bones, int32_t n_bones, int32_t how, int32_t leaf_size,
                  float node_cost, int32_t* order, uint64_t geometry_generation) {
-    static const char* who = "hg_skin_mesh";
-    if (!c) return HG_E_INVALID;
-    if (int rc = hg_ctx_flush(c)) return rc;
-    hg_ctx::VertexBinding* b = nullptr;
-    if (int rc = skin_check(c, who, mesh_index, bones, n_bones, how, b)) return rc;
-    if (int rc = stage(c, c->deform_bones, bones, size_t(n_bones) * HG_SKIN_BONE_FLOATS * sizeof(float))) return rc;
-    if (int rc = skin_device(c, mesh_index, *b, c->deform_bones.p, how, leaf_size, node_cost, nullptr, geometry_generation))
-        return rc;
-    return order_to_host(c, how, order, b->n_tris);
+    return update_mesh(c, {"hg_skin_mesh", mesh_index, MeshUpdate::kBones, bones, nullptr, n_bones, false, how, leaf_size,
+                           node_cost, order, geometry_generation});
 }
 
 int hg_mesh_vertices_readback(hg_ctx* c, int32_t mesh_index, float* positions, float* normals, int32_t n_vertices) {

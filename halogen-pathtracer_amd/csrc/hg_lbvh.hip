@@ -1,6 +1,8 @@
 // hg_lbvh.hip — hg_rebuild_mesh / hg_rebuild_mesh_device: a new tree for one mesh of the device scene, built on the
 // device over the mesh's own triangle and record storage (the contract: hg_lbvh.h; the host twin: hg_build_blas_lbvh,
-// hg_host.cpp).  Not in the reference.
+// hg_host.cpp).  Not in the reference.  Here: the kernels, the two builds (build_lbvh_device, build_sah_device: step 5
+// of update_mesh, hg_refit.hip, which checks before them and adopts the tree after them) and the four entry points,
+// which fill a MeshUpdate.
 //
 // The build, all on the context stream and ordered by it alone (no float atomics, no kernel that waits on another
 // workgroup): key points and per-workgroup bounds, the final bounds in one small workgroup, the Morton codes, rocprim's
@@ -11,7 +13,8 @@
 // hg_rebuild_mesh_sah / hg_rebuild_mesh_sah_device (the second contract of hg_lbvh.h; the twin: hg_build_blas_lbvh_sah):
 // the same order, the radix tree at L = 1 in scratch, one lane per internal node deciding the small subtrees below it,
 // rocprim's exclusive scan of the live flags, whose total the host reads to pick the rung of the node cost ladder and
-// to refuse a tree that does not fit, then one lane per live node writing its record; the same refit.
+// to refuse a tree that does not fit (HgMeshTrees::check_sah_records), then one lane per live node writing its record;
+// the same refit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,8 +33,6 @@ using namespace hgrt;
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kTriWords = 18;  // floats of a HalogenTriangle
-static_assert(sizeof(HalogenTriangle) == 72, "the kernels move a triangle as 18 floats");
 
 // pmin / pmax of the workgroup's 256 lanes: s[k][tid] holds lane tid's value of component k (0..2 min, 3..5 max)
 __device__ void block_bounds(float (*s)[kBlock], uint32_t tid) {
@@ -221,51 +222,6 @@ __global__ __launch_bounds__(kBlock) void hg_lbvh_sah_emit(const HgLbvhNode* __r
     refs[j] = make_uint2(ref[0], ref[1]);
 }
 
-struct RebuildArgs {
-    hg_ctx::RebuildSlot slot;
-    uint32_t L = 0, K = 0;
-};
-
-// What both kinds of rebuild check after a refit's checks and their own argument's: the triangle count, the range of
-// inline leaf refs; and the tree's slot of records
-int rebuild_check_mesh(hg_ctx* c, int32_t mesh_index, int32_t n_tris, const hg_ctx::RefitTree* tree,
-                       hg_ctx::RebuildSlot& slot) {
-    if (uint32_t(n_tris) != tree->plan.extent || n_tris == 0)
-        return fail(c, HG_E_INVALID, "hg_rebuild_mesh: mesh %d: %d triangles, its tree holds %u", mesh_index, n_tris,
-                    tree->plan.extent);
-    const HgDevMesh& dm = c->dev_meshes[size_t(mesh_index)];
-    if (uint64_t(dm.tri_offset) + uint64_t(n_tris) > uint64_t(HG_LBVH_MAX_TRIS))
-        return fail(c, HG_E_UNSUPPORTED, "hg_rebuild_mesh: mesh %d: triangles %u + %d past 2^27 (inline leaves only)",
-                    mesh_index, dm.tri_offset, n_tris);
-    auto it = c->rebuild_slots.find(dm.tri_offset);
-    if (it != c->rebuild_slots.end()) {
-        slot = it->second;
-    } else {  // not rebuilt since the last full upload: the plan is the uploaded tree's
-        slot.rec_min = tree->plan.records.empty() ? 0u : tree->plan.rec_min;
-        slot.capacity = tree->plan.records.empty() ? 0u : tree->plan.rec_span;
-    }
-    return HG_OK;
-}
-
-// Everything a rebuild checks before the first device write: a refit's checks, then its own
-int rebuild_check(hg_ctx* c, int32_t mesh_index, const void* tris, int32_t n_tris, int32_t leaf_size,
-                  std::vector<int32_t>& instances, RebuildArgs& a) {
-    hg_ctx::RefitTree* tree = nullptr;
-    if (int rc = refit_check(c, mesh_index, tris, n_tris, tree, instances)) return rc;
-    if (leaf_size < 0 || leaf_size > int32_t(HG_LBVH_MAX_LEAF))
-        return fail(c, HG_E_INVALID, "hg_rebuild_mesh: leaf_size %d outside 0..%u", leaf_size, HG_LBVH_MAX_LEAF);
-    if (int rc = rebuild_check_mesh(c, mesh_index, n_tris, tree, a.slot)) return rc;
-    a.L = leaf_size ? uint32_t(leaf_size) : hg_lbvh_auto_leaf(uint32_t(n_tris), a.slot.capacity);
-    if (a.L == 0)
-        return fail(c, HG_E_UNSUPPORTED, "hg_rebuild_mesh: mesh %d: no leaf size up to %u fits %d triangles into %u records",
-                    mesh_index, HG_LBVH_MAX_LEAF, n_tris, a.slot.capacity);
-    a.K = hg_lbvh_leaf_count(uint32_t(n_tris), a.L);
-    if (a.K - 1 > a.slot.capacity)
-        return fail(c, HG_E_UNSUPPORTED, "hg_rebuild_mesh: mesh %d: %u records at leaf size %u, the tree's capacity is %u",
-                    mesh_index, a.K - 1, a.L, a.slot.capacity);
-    return HG_OK;
-}
-
 // The order of both kinds of rebuild, into the context's scratch (nothing of the scene is written): key points, bounds,
 // codes, the sort.  Leaves the sorted codes in c->lbvh.codes_sorted and the order in c->lbvh.index_sorted, and
 // c->lbvh.tris large enough for the gather.
@@ -306,111 +262,40 @@ int sort_device(hg_ctx* c, const void* d_tris, uint32_t n) {
     return HG_OK;
 }
 
-int finish_device(hg_ctx* c, int32_t mesh_index, const std::vector<int32_t>& instances, const hg_ctx::RebuildSlot& slot,
-                  uint32_t n_records, int32_t n_tris, uint64_t geometry_generation);
+}  // namespace
 
-// The build and the refit, for a quiesced context.  d_tris: n_tris HalogenTriangle on the device, 4-byte aligned;
-// d_order: optional.  The order is left in c->lbvh.index_sorted as well.
-int rebuild_device(hg_ctx* c, int32_t mesh_index, const std::vector<int32_t>& instances, const RebuildArgs& a,
-                   const void* d_tris, int32_t n_tris, void* d_order, uint64_t geometry_generation) {
+namespace hgrt {
+
+// The records and the sorted triangles of a rebuild with K leaves of L, for a quiesced context.  d_tris: n
+// HalogenTriangle on the device, 4-byte aligned; d_order: optional.  Leaves the K - 1 records' refs in c->lbvh.refs, the
+// triangles in the new order in c->lbvh.tris and the order in c->lbvh.index_sorted.
+int build_lbvh_device(hg_ctx* c, uint32_t tri_offset, const HgMeshTrees::Slot& slot, uint32_t L, uint32_t K,
+                      const void* d_tris, uint32_t n, void* d_order) {
     hg_ctx::Lbvh& B = c->lbvh;
-    const uint32_t n = uint32_t(n_tris), L = a.L, K = a.K, rec_min = a.slot.rec_min;
-    const HgDevMesh first = c->dev_meshes[size_t(instances[0])];
     const uint32_t blocks = (n + kBlock - 1) / kBlock;
     if (int rc = ensure(c, B.refs, size_t(K) * sizeof(uint2))) return rc;
     c->guides_valid = false;
     if (int rc = sort_device(c, d_tris, n)) return rc;
-    const float* src = static_cast<const float*>(d_tris);
     c->geometry_stale = true;  // (from the next launch on the device is no longer the last upload's, whatever fails)
     if (K > 1) {
         hipLaunchKernelGGL(hg_lbvh_topology, dim3((K - 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
-                           static_cast<const uint32_t*>(B.codes_sorted.p), n, L, K, rec_min, first.tri_offset,
+                           static_cast<const uint32_t*>(B.codes_sorted.p), n, L, K, slot.rec_min, tri_offset,
                            static_cast<float4*>(c->nodes.p), static_cast<uint2*>(B.refs.p));
         HG_HIP(c, hipGetLastError());
     }
-    hipLaunchKernelGGL(hg_lbvh_gather, dim3(blocks), dim3(kBlock), 0, c->stream, src,
+    hipLaunchKernelGGL(hg_lbvh_gather, dim3(blocks), dim3(kBlock), 0, c->stream, static_cast<const float*>(d_tris),
                        static_cast<const uint32_t*>(B.index_sorted.p), n, static_cast<float*>(B.tris.p),
                        static_cast<int32_t*>(d_order));
     HG_HIP(c, hipGetLastError());
-    return finish_device(c, mesh_index, instances, a.slot, K - 1, n_tris, geometry_generation);
-}
-
-// What follows the records of either kind of rebuild: n_records records from slot.rec_min on hold the new tree's refs
-// (c->lbvh.refs has the compact copy) and c->lbvh.tris the triangles in the new order.  The host's picture of the new
-// topology (the records' refs, the tree's plan, the root of every instance), then the refit.
-int finish_device(hg_ctx* c, int32_t mesh_index, const std::vector<int32_t>& instances, const hg_ctx::RebuildSlot& slot,
-                  uint32_t n_records, int32_t n_tris, uint64_t geometry_generation) {
-    hg_ctx::Lbvh& B = c->lbvh;
-    const uint32_t n = uint32_t(n_tris), rec_min = slot.rec_min;
-    const HgDevMesh first = c->dev_meshes[size_t(instances[0])];
-    int rc;
-    std::vector<uint32_t> refs(size_t(n_records) * 2);
-    if (n_records)
-        HG_HIP(c, hipMemcpyAsync(refs.data(), B.refs.p, refs.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HG_HIP(c, hipStreamSynchronize(c->stream));
-    if (!refs.empty()) std::memcpy(&c->rec_refs[size_t(rec_min) * 2], refs.data(), refs.size() * 4);
-    const uint32_t root = n_records ? rec_min : (HG_LEAF_BIT | (n << HG_LEAF_CNT_SHIFT) | first.tri_offset);
-    hg_ctx::RefitTree t;
-    if (!hg_refit_plan(c->rec_refs.data(), c->rec_refs.size() / 2, c->leaf_table.data(), c->leaf_table.size() / 2, root,
-                       first.tri_offset, t.plan)) {
-        // (cannot happen for sorted keys; the tree's records are overwritten, so the context is left without a scene
-        // and nothing else of its bookkeeping is touched: the next call is a full upload)
-        c->has_scene = false;
-        return fail(c, HG_E_INVALID, "hg_rebuild_mesh: mesh %d: the rebuilt records are not a tree; upload the scene again",
-                    mesh_index);
-    }
-    c->rebuild_slots[first.tri_offset] = slot;
-    // the old tree's plan goes; its device list is kept for the new plan (the same size at the same leaf size: no
-    // free and allocation, which would synchronise the device, per rebuild)
-    const uint64_t old_key = (uint64_t(first.root_ref) << 32) | first.tri_offset;
-    auto old = c->refit_trees.find(old_key);
-    if (old != c->refit_trees.end()) {
-        t.list = old->second.list;
-        c->refit_trees.erase(old);
-    }
-    if (t.plan.records.empty()) release(t.list);
-    for (int32_t j : instances) c->dev_meshes[size_t(j)].root_ref = root;
-    hg_ctx::RefitTree& tree = c->refit_trees[(uint64_t(root) << 32) | first.tri_offset] = std::move(t);
-    if (!tree.plan.records.empty())
-        if ((rc = upload(c, tree.list, tree.plan.records.data(), tree.plan.records.size() * sizeof(uint32_t)))) return rc;
-    if ((rc = refit_device(c, tree, instances, B.tris.p, n_tris, geometry_generation))) return rc;
-    // an index list bound to the tree (hg_set_mesh_vertices) follows the triangles into the new order
-    if ((rc = deform_follow_order(c, first.tri_offset, static_cast<const uint32_t*>(B.index_sorted.p), n))) return rc;
-    // the traversal's stack: what a full upload of the scene with this tree sets (every mesh's tree has its plan cached:
-    // refit_check walked the others)
-    uint32_t max_depth = 0;
-    for (const HgDevMesh& m : c->dev_meshes) {
-        auto it = c->refit_trees.find((uint64_t(m.root_ref) << 32) | m.tri_offset);
-        if (it != c->refit_trees.end() && !it->second.plan.level_off.empty())
-            max_depth = std::max(max_depth, uint32_t(it->second.plan.level_off.size() - 1));
-    }
-    c->stack_depth = hg_stack_depth(max_depth);
-    c->scene_rebuilds++;
     return HG_OK;
 }
 
-// Everything hg_rebuild_mesh_sah* checks before the first device launch: a refit's checks, the node cost, what every
-// rebuild checks.  (Whether the live records fit is known only after the collapse: rebuild_sah_device refuses that,
-// still before the first write to the scene.)
-int rebuild_sah_check(hg_ctx* c, int32_t mesh_index, const void* tris, int32_t n_tris, float node_cost,
-                      std::vector<int32_t>& instances, hg_ctx::RebuildSlot& slot) {
-    hg_ctx::RefitTree* tree = nullptr;
-    if (int rc = refit_check(c, mesh_index, tris, n_tris, tree, instances)) return rc;
-    if (!(node_cost >= 0.0f) || node_cost == hg_u2f(0x7F800000u))
-        return fail(c, HG_E_INVALID, "hg_rebuild_mesh_sah: node_cost %g is negative or not finite", double(node_cost));
-    return rebuild_check_mesh(c, mesh_index, n_tris, tree, slot);
-}
-
-// The build with leaves chosen by surface area and the refit, for a quiesced context.  The order, the gather into
-// scratch, the L = 1 tree, and per rung of the ladder the collapse, the scan and the live count, which the host reads:
-// all of it in the context's scratch, so a tree that does not fit is refused with the scene as it was.  Then the
-// records, the caller's order, and what every rebuild ends with.
-int rebuild_sah_device(hg_ctx* c, int32_t mesh_index, const std::vector<int32_t>& instances,
-                       const hg_ctx::RebuildSlot& slot, float node_cost, const void* d_tris, int32_t n_tris,
-                       void* d_order, uint64_t geometry_generation) {
+// The same with leaves chosen by surface area.  The order, the gather into scratch, the L = 1 tree, and per rung of the
+// ladder the collapse, the scan and the live count, which the host reads: all of it in the context's scratch, so a tree
+// that does not fit is refused with the scene as it was.  Then the n_records records and the caller's order.
+int build_sah_device(hg_ctx* c, int32_t mesh_index, uint32_t tri_offset, const HgMeshTrees::Slot& slot, float node_cost,
+                     const void* d_tris, uint32_t n, void* d_order, uint32_t& n_records) {
     hg_ctx::Lbvh& B = c->lbvh;
-    const uint32_t n = uint32_t(n_tris);
-    const HgDevMesh first = c->dev_meshes[size_t(instances[0])];
     const uint32_t blocks = (n + kBlock - 1) / kBlock, node_blocks = (n - 1 + kBlock - 1) / kBlock;
     int rc;
     if ((rc = sort_device(c, d_tris, n))) return rc;
@@ -452,13 +337,8 @@ int rebuild_sah_device(hg_ctx* c, int32_t mesh_index, const std::vector<int32_t>
             n_live = last[0] + last[1];
             fits = n_live <= slot.capacity;
         }
-        if (!fits && node_cost == 0.0f)
-            return fail(c, HG_E_UNSUPPORTED,
-                        "hg_rebuild_mesh_sah: mesh %d: %u records at node cost %g, the last of the ladder; the tree's "
-                        "capacity is %u", mesh_index, n_live, double(used), slot.capacity);
-        if (!fits)
-            return fail(c, HG_E_UNSUPPORTED, "hg_rebuild_mesh_sah: mesh %d: %u records at node cost %g, the tree's capacity is %u",
-                        mesh_index, n_live, double(used), slot.capacity);
+        HgPackError err;
+        if (HgMeshTrees::check_sah_records(mesh_index, n_live, node_cost, used, slot, err)) return fail(c, err);
     }
     if ((rc = ensure(c, B.refs, size_t(std::max(n_live, 1u)) * sizeof(uint2)))) return rc;
     c->guides_valid = false;
@@ -466,85 +346,43 @@ int rebuild_sah_device(hg_ctx* c, int32_t mesh_index, const std::vector<int32_t>
     if (n_live) {
         hipLaunchKernelGGL(hg_lbvh_sah_emit, dim3(node_blocks), dim3(kBlock), 0, c->stream,
                            static_cast<const HgLbvhNode*>(B.topo.p), static_cast<const uint32_t*>(B.live.p),
-                           static_cast<const uint32_t*>(B.new_index.p), n, slot.rec_min, first.tri_offset,
+                           static_cast<const uint32_t*>(B.new_index.p), n, slot.rec_min, tri_offset,
                            static_cast<float4*>(c->nodes.p), static_cast<uint2*>(B.refs.p));
         HG_HIP(c, hipGetLastError());
     }
     if (d_order)
         HG_HIP(c, hipMemcpyAsync(d_order, B.index_sorted.p, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToDevice,
                                  c->stream));
-    return finish_device(c, mesh_index, instances, slot, n_live, n_tris, geometry_generation);
+    n_records = n_live;
+    return HG_OK;
 }
 
-}  // namespace
+}  // namespace hgrt
 
 extern "C" {
 
 int hg_rebuild_mesh_sah_device(hg_ctx* c, int32_t mesh_index, const void* d_tris, int32_t n_tris, float node_cost,
                                void* d_order, uint64_t geometry_generation) {
-    if (!c) return HG_E_INVALID;
-    if (int rc = hg_ctx_flush(c)) return rc;
-    std::vector<int32_t> instances;
-    hg_ctx::RebuildSlot slot;
-    if (int rc = rebuild_sah_check(c, mesh_index, d_tris, n_tris, node_cost, instances, slot)) return rc;
-    if ((reinterpret_cast<uintptr_t>(d_tris) & 3u) || (reinterpret_cast<uintptr_t>(d_order) & 3u))
-        return fail(c, HG_E_INVALID, "hg_rebuild_mesh_sah_device: the triangle and order arrays must be 4-byte aligned");
-    if (int rc = set_device(c)) return rc;
-    if (int rc = quiesce(c)) return rc;  // no trace in flight reads the arrays rewritten below
-    return rebuild_sah_device(c, mesh_index, instances, slot, node_cost, d_tris, n_tris, d_order, geometry_generation);
+    return update_mesh(c, {"hg_rebuild_mesh_sah_device", mesh_index, MeshUpdate::kTriangles, d_tris, nullptr, n_tris, true,
+                           HG_DEFORM_REBUILD_SAH, 0, node_cost, d_order, geometry_generation});
 }
 
 int hg_rebuild_mesh_sah(hg_ctx* c, int32_t mesh_index, const HalogenTriangle* tris, int32_t n_tris, float node_cost,
                         int32_t* order, uint64_t geometry_generation) {
-    if (!c) return HG_E_INVALID;
-    if (int rc = hg_ctx_flush(c)) return rc;
-    std::vector<int32_t> instances;
-    hg_ctx::RebuildSlot slot;
-    if (int rc = rebuild_sah_check(c, mesh_index, tris, n_tris, node_cost, instances, slot)) return rc;
-    if (int rc = set_device(c)) return rc;
-    if (int rc = quiesce(c)) return rc;
-    const size_t bytes = size_t(n_tris) * sizeof(HalogenTriangle);
-    if (int rc = ensure(c, c->refit_in, bytes)) return rc;
-    HG_HIP(c, hipMemcpyAsync(c->refit_in.p, tris, bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = rebuild_sah_device(c, mesh_index, instances, slot, node_cost, c->refit_in.p, n_tris, nullptr,
-                                    geometry_generation))
-        return rc;
-    if (order)
-        HG_HIP(c, hipMemcpy(order, c->lbvh.index_sorted.p, size_t(n_tris) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return HG_OK;
+    return update_mesh(c, {"hg_rebuild_mesh_sah", mesh_index, MeshUpdate::kTriangles, tris, nullptr, n_tris, false,
+                           HG_DEFORM_REBUILD_SAH, 0, node_cost, order, geometry_generation});
 }
 
 int hg_rebuild_mesh_device(hg_ctx* c, int32_t mesh_index, const void* d_tris, int32_t n_tris, int32_t leaf_size,
                            void* d_order, uint64_t geometry_generation) {
-    if (!c) return HG_E_INVALID;
-    if (int rc = hg_ctx_flush(c)) return rc;
-    std::vector<int32_t> instances;
-    RebuildArgs a;
-    if (int rc = rebuild_check(c, mesh_index, d_tris, n_tris, leaf_size, instances, a)) return rc;
-    if ((reinterpret_cast<uintptr_t>(d_tris) & 3u) || (reinterpret_cast<uintptr_t>(d_order) & 3u))
-        return fail(c, HG_E_INVALID, "hg_rebuild_mesh_device: the triangle and order arrays must be 4-byte aligned");
-    if (int rc = set_device(c)) return rc;
-    if (int rc = quiesce(c)) return rc;  // no trace in flight reads the arrays rewritten below
-    return rebuild_device(c, mesh_index, instances, a, d_tris, n_tris, d_order, geometry_generation);
+    return update_mesh(c, {"hg_rebuild_mesh_device", mesh_index, MeshUpdate::kTriangles, d_tris, nullptr, n_tris, true,
+                           HG_DEFORM_REBUILD, leaf_size, 0.0f, d_order, geometry_generation});
 }
 
 int hg_rebuild_mesh(hg_ctx* c, int32_t mesh_index, const HalogenTriangle* tris, int32_t n_tris, int32_t leaf_size,
                     int32_t* order, uint64_t geometry_generation) {
-    if (!c) return HG_E_INVALID;
-    if (int rc = hg_ctx_flush(c)) return rc;
-    std::vector<int32_t> instances;
-    RebuildArgs a;
-    if (int rc = rebuild_check(c, mesh_index, tris, n_tris, leaf_size, instances, a)) return rc;
-    if (int rc = set_device(c)) return rc;
-    if (int rc = quiesce(c)) return rc;
-    const size_t bytes = size_t(n_tris) * sizeof(HalogenTriangle);
-    if (int rc = ensure(c, c->refit_in, bytes)) return rc;
-    HG_HIP(c, hipMemcpyAsync(c->refit_in.p, tris, bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = rebuild_device(c, mesh_index, instances, a, c->refit_in.p, n_tris, nullptr, geometry_generation))
-        return rc;
-    if (order)
-        HG_HIP(c, hipMemcpy(order, c->lbvh.index_sorted.p, size_t(n_tris) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return HG_OK;
+    return update_mesh(c, {"hg_rebuild_mesh", mesh_index, MeshUpdate::kTriangles, tris, nullptr, n_tris, false,
+                           HG_DEFORM_REBUILD, leaf_size, 0.0f, order, geometry_generation});
 }
 
 }  // extern "C"

@@ -1,9 +1,25 @@
-// hg_refit.hip — deforming geometry: hg_refit_mesh / hg_refit_mesh_device replace one mesh's triangles in the device
-// scene and recompute every box of its tree there, topology unchanged (the contract: hg_refit.h; the host twin:
-// hg_refit_blas, hg_host.cpp); hg_scene_readback hands out the device scene's arrays for tests.  Not in the reference.
+// hg_refit.hip — deforming geometry: the one path of every update of a mesh of the device scene (update_mesh), the
+// refit itself, which every kind of update ends with, and the entry points hg_refit_mesh / hg_refit_mesh_device;
+// hg_scene_readback hands out the device scene's arrays for tests.  Not in the reference.
+//
+// An update replaces one mesh's triangles and recomputes every box of its tree on the device (the contract: hg_refit.h;
+// the host twin: hg_refit_blas, hg_host.cpp), over the old topology (a refit) or a new one (hg_lbvh.hip), from 72-byte
+// triangles or from vertices or a bone palette (hg_deform.hip).  The ten entry points fill a MeshUpdate (hg_rt.h);
+// update_mesh runs, once and in this order:
+//   1  null context, hg_ctx_flush;
+//   2  every refusal that needs no device, with nothing launched or allocated before the last of them: the vertex
+//      binding and skin (hg_deform.hip), the tree (hg_mesh_trees.h, which has no HIP in it and is tested on the CPU),
+//      pointer alignment;
+//   3  set_device, quiesce;
+//   4  the source as triangles on the device: the caller's, staged from the host, or skinned and packed;
+//   5  the refit, or the sort and the build of hg_lbvh.hip (a build by surface area has one late refusal, before the
+//      first write to the scene);
+//   6  for a rebuild: the new tree into the host's picture (HgMeshTrees::adopt), its plan list to the device, the refit,
+//      the bound index list into the new order, stack depth and counters;
+//   7  the order to the host, for the host forms.
 //
 // A translation unit of its own: the traversal kernels compile to what they compile to without it.  The kernels and
-// their launchers first, then the entry points of the C-ABI.
+// their launchers first, then the path, then the entry points of the C-ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,12 +32,9 @@
 
 using namespace hgrt;
 
-static_assert(sizeof(HalogenTriangle) == 72, "the repack kernel moves a triangle as 18 floats");
-
 namespace {
 
 constexpr int kRefitBlock = 256;
-constexpr int kTriWords = 18;  // floats of a HalogenTriangle
 
 // Repack: HalogenTriangle (72 B, AoS) -> the traversal's 9-float (v0, e1, e2) stream and the three normal float4
 // (n0, n1 - n0, n2 - n0), the subtractions of hg_pack_geometry.  A lane-per-triangle read of 72-B structs is a strided
@@ -125,66 +138,13 @@ __global__ __launch_bounds__(kRefitBlock) void hg_refit_level(const uint32_t* __
 
 }  // namespace
 
-namespace hgrt {
+namespace {
 
-// Everything hg_refit_mesh* checks before the first device write.  On success: the tree (its plan built and cached on
-// first use) and the meshes refitted together (the instances of the tree: same root ref, same triangle offset).
-int refit_check(hg_ctx* c, int32_t mesh_index, const void* tris, int32_t n_tris, hg_ctx::RefitTree*& tree,
-                std::vector<int32_t>& instances) {
-    if (!c->has_scene) return fail(c, HG_E_NOSCENE, "hg_refit_mesh: hg_upload_scene not called");
-    if (mesh_index < 0 || mesh_index >= c->n_meshes)
-        return fail(c, HG_E_INVALID, "hg_refit_mesh: mesh_index %d out of range (%d meshes)", mesh_index, c->n_meshes);
-    if (!tris) return fail(c, HG_E_INVALID, "hg_refit_mesh: null triangle array");
-    if (n_tris < 0) return fail(c, HG_E_INVALID, "hg_refit_mesh: negative triangle count");
-    const HgDevMesh& dm = c->dev_meshes[size_t(mesh_index)];
-    const size_t n_rec = c->rec_refs.size() / 2, n_leaf = c->leaf_table.size() / 2;
-    auto plan_of = [&](const HgDevMesh& m, HgRefitPlan& plan) {
-        return hg_refit_plan(c->rec_refs.data(), n_rec, c->leaf_table.data(), n_leaf, m.root_ref, m.tri_offset, plan);
-    };
-    const uint64_t key = (uint64_t(dm.root_ref) << 32) | dm.tri_offset;
-    auto it = c->refit_trees.find(key);
-    if (it == c->refit_trees.end()) {
-        hg_ctx::RefitTree t;
-        if (!plan_of(dm, t.plan)) return fail(c, HG_E_INVALID, "hg_refit_mesh: mesh %d: the device records are not a tree", mesh_index);
-        it = c->refit_trees.emplace(key, std::move(t)).first;
-    }
-    tree = &it->second;
-    if (uint32_t(n_tris) < tree->plan.extent)
-        return fail(c, HG_E_INVALID, "hg_refit_mesh: mesh %d: %d triangles, its tree's leaves reach %u", mesh_index,
-                    n_tris, tree->plan.extent);
-    if (uint64_t(dm.tri_offset) + uint64_t(n_tris) > uint64_t(c->n_tris))
-        return fail(c, HG_E_INVALID, "hg_refit_mesh: mesh %d: triangles %u + %d past the scene's %d", mesh_index,
-                    dm.tri_offset, n_tris, c->n_tris);
-    instances.clear();
-    const uint64_t lo = dm.tri_offset, hi = lo + uint64_t(n_tris);
-    for (int32_t j = 0; j < c->n_meshes; ++j) {
-        const HgDevMesh& o = c->dev_meshes[size_t(j)];
-        if (o.root_ref == dm.root_ref && o.tri_offset == dm.tri_offset) {
-            instances.push_back(j);
-            continue;
-        }
-        // another tree over some of these triangles would go stale
-        const uint64_t okey = (uint64_t(o.root_ref) << 32) | o.tri_offset;
-        auto oit = c->refit_trees.find(okey);
-        if (oit == c->refit_trees.end()) {  // (std::map: `tree` stays valid)
-            hg_ctx::RefitTree t;
-            if (!plan_of(o, t.plan))
-                return fail(c, HG_E_INVALID, "hg_refit_mesh: mesh %d: the device records are not a tree", j);
-            oit = c->refit_trees.emplace(okey, std::move(t)).first;
-        }
-        const uint64_t olo = o.tri_offset, ohi = olo + oit->second.plan.extent;
-        if (olo < hi && lo < ohi)
-            return fail(c, HG_E_UNSUPPORTED,
-                        "hg_refit_mesh: mesh %d shares triangles with mesh %d, which has another tree", mesh_index, j);
-    }
-    return HG_OK;
-}
-
-// Steps 1-5 of a refit with the triangles on the device (d_tris: n_tris HalogenTriangle, at least 4-B aligned)
-int refit_device(hg_ctx* c, hg_ctx::RefitTree& tree, const std::vector<int32_t>& instances, const void* d_tris,
-                 int32_t n_tris, uint64_t geometry_generation) {
+// Steps 1-5 of a refit with the triangles on the device (d_tris: n_tris HalogenTriangle, at least 4-B aligned), for a
+// context that is quiesced.  plan, list: the tree's plan and its records on the device (uploaded here on first use).
+int refit_device(hg_ctx* c, const HgRefitPlan& plan, DevBuf& list, const std::vector<int32_t>& instances,
+                 const void* d_tris, int32_t n_tris, uint64_t geometry_generation) {
     const HgDevMesh first = c->dev_meshes[size_t(instances[0])];
-    const HgRefitPlan& plan = tree.plan;
     c->guides_valid = false;  // the device scene changes: the guide images (hg_update_guides) are another scene's
     // (the tile cost order stays: the geometry moved, the image is similar)
     if (n_tris > 0) {
@@ -201,14 +161,14 @@ int refit_device(hg_ctx* c, hg_ctx::RefitTree& tree, const std::vector<int32_t>&
     }
     HgRootPair pair{};
     if (!plan.records.empty()) {
-        if (!tree.list.p) {
-            if (int rc = upload(c, tree.list, plan.records.data(), plan.records.size() * sizeof(uint32_t))) return rc;
+        if (!list.p) {
+            if (int rc = upload(c, list, plan.records.data(), plan.records.size() * sizeof(uint32_t))) return rc;
         }
         if (int rc = ensure(c, c->refit_raw, size_t(plan.rec_span) * 6 * sizeof(float))) return rc;
         for (size_t h = 1; h < plan.level_off.size(); ++h) {
             const uint32_t begin = plan.level_off[h - 1], end = plan.level_off[h];
             hipLaunchKernelGGL(hg_refit_level, dim3((end - begin + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0,
-                               c->stream, static_cast<const uint32_t*>(tree.list.p), begin, end,
+                               c->stream, static_cast<const uint32_t*>(list.p), begin, end,
                                static_cast<float4*>(c->nodes.p), static_cast<const uint2*>(c->leaves.p),
                                static_cast<const HalogenTriangle*>(d_tris), first.tri_offset, plan.rec_min,
                                static_cast<float*>(c->refit_raw.p));
@@ -234,16 +194,120 @@ int refit_device(hg_ctx* c, hg_ctx::RefitTree& tree, const std::vector<int32_t>&
     return HG_OK;
 }
 
-void refit_reset(hg_ctx* c) {
-    for (auto& kv : c->refit_trees) release(kv.second.list);
-    c->refit_trees.clear();
-    c->rebuild_slots.clear();
-    for (auto& kv : c->vertex_bindings) {
-        hg_ctx::VertexBinding& b = kv.second;
-        for (DevBuf* d : {&b.indices, &b.spare, &b.rest_positions, &b.rest_normals, &b.bone_indices, &b.weights,
-                          &b.positions, &b.normals})
-            release(*d);
+// What follows the records of either kind of rebuild: n_records records from slot.rec_min on hold the new tree's refs
+// (c->lbvh.refs has the compact copy), c->lbvh.tris the triangles in the new order and c->lbvh.index_sorted the order.
+// The host's picture of the new topology (hg_mesh_trees.h), the tree's device list, then the refit.
+int adopt_device(hg_ctx* c, const MeshUpdate& u, const std::vector<int32_t>& instances, const HgMeshTrees::Slot& slot,
+                 uint32_t n_records, int32_t n_tris) {
+    const uint32_t tri_offset = c->dev_meshes[size_t(instances[0])].tri_offset;
+    std::vector<uint32_t> refs(size_t(n_records) * 2);
+    if (n_records)
+        HG_HIP(c, hipMemcpyAsync(refs.data(), c->lbvh.refs.p, refs.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HG_HIP(c, hipStreamSynchronize(c->stream));
+    HgMeshTrees::Adopted tree;
+    HgPackError err;
+    if (c->trees.adopt(c->dev_meshes, u.mesh_index, instances, slot, refs.data(), n_records, uint32_t(n_tris), tree, err)) {
+        // (the tree's records are overwritten, so the context is left without a scene and nothing else of its
+        // bookkeeping is touched: the next call is a full upload)
+        c->has_scene = false;
+        return fail(c, err);
     }
+    // the old tree's device list is kept for the new plan (the same size at the same leaf size: no free and allocation,
+    // which would synchronise the device, per rebuild)
+    DevBuf list;
+    auto old = c->refit_lists.find(tree.old_key);
+    if (old != c->refit_lists.end()) {
+        list = old->second;
+        c->refit_lists.erase(old);
+    }
+    const std::vector<uint32_t>& records = tree.plan->records;
+    if (records.empty()) release(list);
+    DevBuf& kept = c->refit_lists[tree.new_key] = list;
+    int rc;
+    if (!records.empty())
+        if ((rc = upload(c, kept, records.data(), records.size() * sizeof(uint32_t)))) return rc;
+    if ((rc = refit_device(c, *tree.plan, kept, instances, c->lbvh.tris.p, n_tris, u.generation))) return rc;
+    // an index list bound to the tree (hg_set_mesh_vertices) follows the triangles into the new order
+    if ((rc = deform_follow_order(c, tri_offset, static_cast<const uint32_t*>(c->lbvh.index_sorted.p), uint32_t(n_tris))))
+        return rc;
+    c->stack_depth = tree.stack_depth;
+    c->scene_rebuilds++;
+    return HG_OK;
+}
+
+}  // namespace
+
+namespace hgrt {
+
+// The one path of every mesh update; the steps are numbered as in this file's header
+int update_mesh(hg_ctx* c, const MeshUpdate& u) {
+    if (!c) return HG_E_INVALID;
+    if (int rc = hg_ctx_flush(c)) return rc;  // 1
+    // 2: every refusal that needs no device; nothing is launched or allocated before the last of them
+    const bool from_tris = u.source == MeshUpdate::kTriangles;
+    hg_ctx::VertexBinding* binding = nullptr;
+    if (!from_tris)
+        if (int rc = vertex_source_check(c, u, binding)) return rc;
+    const int32_t n_tris = from_tris ? u.count : binding->n_tris;
+    const bool have_tris = !from_tris || u.a;
+    HgPackError err;
+    const HgRefitPlan* plan = nullptr;
+    std::vector<int32_t> instances;
+    HgMeshTrees::Slot slot;
+    uint32_t L = 0, K = 0;
+    const int refused =
+        u.how == HG_DEFORM_REBUILD
+            ? c->trees.check_rebuild(c->has_scene, c->dev_meshes, u.mesh_index, have_tris, n_tris, u.leaf_size, instances,
+                                     slot, L, K, err)
+        : u.how == HG_DEFORM_REBUILD_SAH
+            ? c->trees.check_rebuild_sah(c->has_scene, c->dev_meshes, u.mesh_index, have_tris, n_tris, u.node_cost,
+                                         instances, slot, err)
+            : c->trees.check_refit(c->has_scene, c->dev_meshes, u.mesh_index, have_tris, n_tris, plan, instances, err);
+    if (refused) return fail(c, err);
+    if (u.device && ((reinterpret_cast<uintptr_t>(u.a) | reinterpret_cast<uintptr_t>(u.b) |
+                      reinterpret_cast<uintptr_t>(u.order)) & 3u)) {
+        static const char* const arrays[3] = {"triangle and order arrays", "position, normal and order arrays",
+                                              "bone and order arrays"};
+        return fail(c, HG_E_INVALID, "%s: the %s must be 4-byte aligned", u.who,
+                    from_tris && u.how == HG_DEFORM_REFIT ? "triangle array" : arrays[u.source]);
+    }
+    if (int rc = set_device(c)) return rc;  // 3
+    if (int rc = quiesce(c)) return rc;     // no trace in flight reads the arrays rewritten below
+    // 4: the source as triangles on the device
+    const void* d_tris = u.a;
+    if (!from_tris || !u.device) {
+        const size_t bytes = size_t(n_tris) * sizeof(HalogenTriangle);
+        if (int rc = ensure(c, c->refit_in, bytes)) return rc;
+        d_tris = c->refit_in.p;
+        if (!from_tris) {
+            if (int rc = vertex_source_device(c, u, *binding)) return rc;
+        } else if (bytes) {
+            HG_HIP(c, hipMemcpyAsync(c->refit_in.p, u.a, bytes, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    // 5, 6
+    if (u.how == HG_DEFORM_REFIT)
+        return refit_device(c, *plan, c->refit_lists[HgMeshTrees::key(c->dev_meshes[size_t(u.mesh_index)])], instances,
+                            d_tris, n_tris, u.generation);
+    const uint32_t tri_offset = c->dev_meshes[size_t(instances[0])].tri_offset;
+    void* d_order = u.device ? u.order : nullptr;
+    uint32_t n_records = K - 1;
+    if (int rc = u.how == HG_DEFORM_REBUILD
+                     ? build_lbvh_device(c, tri_offset, slot, L, K, d_tris, uint32_t(n_tris), d_order)
+                     : build_sah_device(c, u.mesh_index, tri_offset, slot, u.node_cost, d_tris, uint32_t(n_tris), d_order,
+                                        n_records))
+        return rc;
+    if (int rc = adopt_device(c, u, instances, slot, n_records, n_tris)) return rc;
+    if (!u.device && u.order)  // 7
+        HG_HIP(c, hipMemcpy(u.order, c->lbvh.index_sorted.p, size_t(n_tris) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return HG_OK;
+}
+
+void refit_reset(hg_ctx* c) {
+    for (auto& kv : c->refit_lists) release(kv.second);
+    c->refit_lists.clear();
+    c->trees.clear();
+    for (auto& kv : c->vertex_bindings) release_binding(kv.second);
     c->vertex_bindings.clear();
 }
 
@@ -253,31 +317,14 @@ extern "C" {
 
 int hg_refit_mesh_device(hg_ctx* c, int32_t mesh_index, const void* d_tris, int32_t n_tris,
                          uint64_t geometry_generation) {
-    if (!c) return HG_E_INVALID;
-    if (int rc = hg_ctx_flush(c)) return rc;
-    hg_ctx::RefitTree* tree = nullptr;
-    std::vector<int32_t> instances;
-    if (int rc = refit_check(c, mesh_index, d_tris, n_tris, tree, instances)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_tris) & 3u)
-        return fail(c, HG_E_INVALID, "hg_refit_mesh_device: the triangle array must be 4-byte aligned");
-    if (int rc = set_device(c)) return rc;
-    if (int rc = quiesce(c)) return rc;  // no trace in flight reads the arrays rewritten below
-    return refit_device(c, *tree, instances, d_tris, n_tris, geometry_generation);
+    return update_mesh(c, {"hg_refit_mesh_device", mesh_index, MeshUpdate::kTriangles, d_tris, nullptr, n_tris, true,
+                           HG_DEFORM_REFIT, 0, 0.0f, nullptr, geometry_generation});
 }
 
 int hg_refit_mesh(hg_ctx* c, int32_t mesh_index, const HalogenTriangle* tris, int32_t n_tris,
                   uint64_t geometry_generation) {
-    if (!c) return HG_E_INVALID;
-    if (int rc = hg_ctx_flush(c)) return rc;
-    hg_ctx::RefitTree* tree = nullptr;
-    std::vector<int32_t> instances;
-    if (int rc = refit_check(c, mesh_index, tris, n_tris, tree, instances)) return rc;
-    if (int rc = set_device(c)) return rc;
-    if (int rc = quiesce(c)) return rc;
-    const size_t bytes = size_t(n_tris) * sizeof(HalogenTriangle);
-    if (int rc = ensure(c, c->refit_in, bytes)) return rc;
-    if (bytes) HG_HIP(c, hipMemcpyAsync(c->refit_in.p, tris, bytes, hipMemcpyHostToDevice, c->stream));
-    return refit_device(c, *tree, instances, c->refit_in.p, n_tris, geometry_generation);
+    return update_mesh(c, {"hg_refit_mesh", mesh_index, MeshUpdate::kTriangles, tris, nullptr, n_tris, false,
+                           HG_DEFORM_REFIT, 0, 0.0f, nullptr, geometry_generation});
 }
 
 int hg_scene_readback(hg_ctx* c, int32_t which, void* dst, size_t capacity, size_t* n_bytes) {

@@ -1,7 +1,7 @@
 // hg_rt.h — what the runtime's translation units (hg_runtime.hip, hg_render.hip, hg_display.hip, hg_query.hip,
-// hg_denoise.hip, hg_refit.hip, hg_lbvh.hip, hg_deform.hip, hg_comm.hip) share over a context: private to libhalogen_hip.so, none of it in the C-ABI.  The
-// helpers are in namespace hgrt (each is defined in the file named beside it); the hg_ctx_* functions are the
-// context's services to hg_comm.hip and to each other.
+// hg_denoise.hip, hg_refit.hip, hg_lbvh.hip, hg_deform.hip, hg_comm.hip) share over a context: private to
+// libhalogen_hip.so, none of it in the C-ABI.  The helpers are in namespace hgrt (each is defined in the file named
+// beside it); the hg_ctx_* functions are the context's services to hg_comm.hip and to each other.
 #pragma once
 #include "hg_ctx.h"
 #include "hg_pair_guard.h"
@@ -23,8 +23,9 @@ using EventPair = std::pair<hipEvent_t, hipEvent_t>;
 using EventGuard = HgPairGuard<EventPair>;  // a timing pair that goes back to free_events unless handed on
 
 // ---- hg_runtime.hip ----
-// Keep the text as the context's last error; returns `code`
+// Keep the text as the context's last error; returns `code`.  Or a refusal of the host-only headers, as it stands
 int fail(hg_ctx* c, int code, const char* fmt, ...);
+int fail(hg_ctx* c, const HgPackError& err);
 
 #define HG_HIP(ctx, call)                                                                                    \
     do {                                                                                                     \
@@ -77,20 +78,47 @@ constexpr int64_t kQueryChunk = int64_t(1) << 20;  // records per launch (and pe
 int query_begin(hg_ctx* c);
 int query_params(hg_ctx* c, uint32_t threads, HgKernelParams& kp);
 
-// ---- hg_refit.hip ----
-// Forget the refit plans of the device scene and free their device lists (a full upload lays the records out anew)
-void refit_reset(hg_ctx* c);
-// Everything hg_refit_mesh* checks before the first device write.  On success: the tree (its plan built and cached on
-// first use; every other tree's plan is cached too) and the meshes refitted together.  Then the refit itself, from
-// n_tris HalogenTriangle on the device (4-byte aligned), for a context that is quiesced (hg_lbvh.hip runs both too)
-int refit_check(hg_ctx* c, int32_t mesh_index, const void* tris, int32_t n_tris, hg_ctx::RefitTree*& tree,
-                std::vector<int32_t>& instances);
-int refit_device(hg_ctx* c, hg_ctx::RefitTree& tree, const std::vector<int32_t>& instances, const void* d_tris,
-                 int32_t n_tris, uint64_t geometry_generation);
+// ---- mesh updates: hg_refit.hip, hg_lbvh.hip, hg_deform.hip ----
+constexpr int kTriWords = 18;  // floats of a HalogenTriangle
+static_assert(sizeof(HalogenTriangle) == 72, "the kernels move a triangle as 18 floats");
 
-// ---- hg_deform.hip ----
+// One update of one mesh of the device scene: what the ten entry points hg_refit_mesh, hg_rebuild_mesh,
+// hg_rebuild_mesh_sah, hg_deform_mesh, hg_skin_mesh and their _device forms fill in
+struct MeshUpdate {
+    const char* who;  // the entry point, for its messages
+    int32_t mesh_index;
+    enum Source { kTriangles, kVertices, kBones } source;
+    const void* a;  // `count` 72-byte triangles | vertex positions | row-major 3 x 4 bone matrices
+    const void* b;  // nullptr                   | vertex normals   | nullptr
+    int32_t count;
+    bool device;    // a, b and order are device pointers (else host pointers)
+    int32_t how;    // HG_DEFORM_REFIT, HG_DEFORM_REBUILD (leaf_size) or HG_DEFORM_REBUILD_SAH (node_cost)
+    int32_t leaf_size;
+    float node_cost;
+    void* order;  // optional: where a rebuild's order goes
+    uint64_t generation;
+};
+// The one path of them all (hg_refit.hip; its header has the steps)
+int update_mesh(hg_ctx* c, const MeshUpdate& u);
+// Forget the trees of the device scene, their device lists and the vertex bindings (a full upload lays the records out
+// anew) (hg_refit.hip)
+void refit_reset(hg_ctx* c);
+// The two kinds of build of a rebuild, for a quiesced context, from n triangles on the device: the new records' refs
+// into the scene's nodes from slot.rec_min on and, compact, into c->lbvh.refs; the triangles in the new order into
+// c->lbvh.tris; the order into c->lbvh.index_sorted and d_order (optional).  By surface area: refuses, before the first
+// write to the scene, a tree whose n_records do not fit the slot (hg_lbvh.hip)
+int build_lbvh_device(hg_ctx* c, uint32_t tri_offset, const HgMeshTrees::Slot& slot, uint32_t L, uint32_t K,
+                      const void* d_tris, uint32_t n, void* d_order);
+int build_sah_device(hg_ctx* c, int32_t mesh_index, uint32_t tri_offset, const HgMeshTrees::Slot& slot, float node_cost,
+                     const void* d_tris, uint32_t n, void* d_order, uint32_t& n_records);
+// An update whose source is vertices or a bone palette: the checks of the source (the binding first), and the source as
+// the binding's triangles in c->refit_in on the context stream (hg_deform.hip)
+int vertex_source_check(hg_ctx* c, const MeshUpdate& u, hg_ctx::VertexBinding*& b);
+int vertex_source_device(hg_ctx* c, const MeshUpdate& u, hg_ctx::VertexBinding& b);
+void release_binding(hg_ctx::VertexBinding& b);
 // After a rebuild of the tree at `tri_offset`: if an index list is bound to it (hg_set_mesh_vertices), permute it on the
 // context stream by the rebuild's order (d_order: n_tris uint32 on the device), so it stays in the tree's triangle order
+// (hg_deform.hip)
 int deform_follow_order(hg_ctx* c, uint32_t tri_offset, const uint32_t* d_order, uint32_t n_tris);
 
 }  // namespace hgrt

@@ -42,6 +42,8 @@ int fail(hg_ctx* c, int code, const char* fmt, ...) {
     return code;
 }
 
+int fail(hg_ctx* c, const HgPackError& err) { return fail(c, err.code, "%s", err.text.c_str()); }
+
 int set_device(hg_ctx* c) {
     HG_HIP(c, hipSetDevice(c->device));
     return HG_OK;
@@ -312,8 +314,6 @@ int hg_upload_scene(hg_ctx* c, const HalogenSphere* spheres, int32_t n_spheres, 
 
 namespace {
 
-int fail(hg_ctx* c, const HgPackError& err) { return hgrt::fail(c, err.code, "%s", err.text.c_str()); }
-
 // The bookkeeping of an upload whose device copies are on the stream: the retained host copies the next upload compares
 // against (made while the device copies run), the mesh table a partial re-upload starts from, counters and counts
 int commit_scene(hg_ctx* c, const HgSceneIn& in, HgScenePack& pack, HgUploadDecision d, uint64_t geometry_generation) {
@@ -327,17 +327,10 @@ int commit_scene(hg_ctx* c, const HgSceneIn& in, HgScenePack& pack, HgUploadDeci
         c->scene_uploads_vouched += d.vouched ? 1u : 0u;
     } else {
         c->stack_depth = pack.stack_depth;
-        c->n_tris = in.n_tris;
         c->n_nodes = in.n_nodes;
-        // what a refit reads of this layout (hg_refit.hip); the caller's arrays describe the device again
+        // what a mesh update reads of this layout (hg_mesh_trees.h); the caller's arrays describe the device again
         refit_reset(c);
-        c->rec_refs.resize(pack.rec.size() / 2);
-        for (size_t r = 0; r < pack.rec.size() / 4; ++r) {
-            std::memcpy(&c->rec_refs[2 * r], &pack.rec[4 * r].w, 4);
-            std::memcpy(&c->rec_refs[2 * r + 1], &pack.rec[4 * r + 1].w, 4);
-        }
-        c->leaf_table.resize(pack.leaf.size() * 2);
-        std::memcpy(c->leaf_table.data(), pack.leaf.data(), pack.leaf.size() * sizeof(uint2));
+        c->trees.reset(pack.rec, pack.leaf, in.n_tris);
         const size_t bytes[4] = {pack.rec.size() * sizeof(float4), pack.leaf.size() * sizeof(uint2),
                                  pack.t9.size() * sizeof(float), pack.nrm.size() * sizeof(float4)};
         std::memcpy(c->geometry_bytes, bytes, sizeof bytes);
@@ -373,7 +366,7 @@ int hg_upload_scene_gen(hg_ctx* c, uint64_t geometry_generation, const HalogenSp
     if (hg_scene_check_limits(in, err)) return fail(c, err);
     const bool stale = c->geometry_stale;  // refitted since the last full upload (hg_refit.hip)
     const HgUploadDecision d = hg_upload_decide_refit(c->has_scene, stale, c->scene_copy, c->geometry_gen,
-                                                      c->dev_meshes.size(), c->n_tris, c->n_nodes, in,
+                                                      c->dev_meshes.size(), c->trees.n_tris, c->n_nodes, in,
                                                       geometry_generation);
     if (d.kind == HG_UPLOAD_SKIP) {
         c->scene_uploads_skipped++;

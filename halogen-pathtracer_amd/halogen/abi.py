@@ -477,24 +477,13 @@ class Context:
         triangle ((n, 18) float32).  triangles as a contiguous (n, 18) float32 torch tensor on the context's device: read
         in place through the device entry point.  generation: the geometry generation the next (vouched) upload_scene
         will carry.  The accumulation is not cleared."""
-        if hasattr(triangles, "data_ptr") and not isinstance(triangles, np.ndarray):
-            import torch
-
-            if not (triangles.is_cuda and triangles.device.index == self.device and triangles.dtype == torch.float32 and
-                    triangles.dim() == 2 and triangles.shape[1] == 18 and triangles.is_contiguous()):
-                raise ValueError(f"device triangles must be a contiguous (n, 18) float32 tensor on cuda:{self.device}")
-            torch.cuda.current_stream(triangles.device).synchronize()  # the triangles are complete before the call
-            self._check(lib().hg_refit_mesh_device(self._h, int(mesh_index), C.c_void_p(triangles.data_ptr()),
-                                                   triangles.shape[0], int(generation)), "hg_refit_mesh_device")
-            return
-        if isinstance(triangles, np.ndarray):
-            a = np.ascontiguousarray(triangles)
-            if a.nbytes % C.sizeof(HalogenTriangle):
-                raise ValueError("triangles must hold 72 bytes per triangle")
-            n, keep = a.nbytes // C.sizeof(HalogenTriangle), a
+        keep, ptr, n, dev = self._triangles(triangles)  # (keep: what ptr points into, alive through the call)
+        if dev:
+            self._stream_done(keep)
+            self._check(lib().hg_refit_mesh_device(self._h, int(mesh_index), ptr, n, int(generation)),
+                        "hg_refit_mesh_device")
         else:
-            n, keep = len(triangles), triangles
-        self._check(lib().hg_refit_mesh(self._h, int(mesh_index), _ptr(keep), n, int(generation)), "hg_refit_mesh")
+            self._check(lib().hg_refit_mesh(self._h, int(mesh_index), ptr, n, int(generation)), "hg_refit_mesh")
 
     def rebuild_mesh(self, mesh_index: int, triangles, leaf_size: int = 0, generation: int = 0):
         """Give mesh `mesh_index` of the uploaded scene a new tree over its moved triangles, built on the device in place
@@ -515,29 +504,38 @@ class Context:
     def _rebuild(self, name, mesh_index, triangles, arg, generation):
         """hg_rebuild_mesh / hg_rebuild_mesh_sah (`arg`: the leaf size / the node cost), or the _device form for a
         torch tensor."""
-        if hasattr(triangles, "data_ptr") and not isinstance(triangles, np.ndarray):
+        keep, ptr, n, dev = self._triangles(triangles)
+        if dev:
             import torch
 
-            if not (triangles.is_cuda and triangles.device.index == self.device and triangles.dtype == torch.float32 and
-                    triangles.dim() == 2 and triangles.shape[1] == 18 and triangles.is_contiguous()):
-                raise ValueError(f"device triangles must be a contiguous (n, 18) float32 tensor on cuda:{self.device}")
-            order = torch.empty(triangles.shape[0], dtype=torch.int32, device=triangles.device)
-            torch.cuda.current_stream(triangles.device).synchronize()  # the triangles are complete before the call
-            self._check(getattr(lib(), name + "_device")(self._h, int(mesh_index), C.c_void_p(triangles.data_ptr()),
-                                                         triangles.shape[0], arg, C.c_void_p(order.data_ptr()),
-                                                         int(generation)), name + "_device")
-            return order
+            order = torch.empty(n, dtype=torch.int32, device=keep.device)
+            name, order_ptr = name + "_device", C.c_void_p(order.data_ptr())
+            self._stream_done(keep)
+        else:
+            order = np.zeros(n, dtype=np.int32)
+            order_ptr = _ptr(order)
+        self._check(getattr(lib(), name)(self._h, int(mesh_index), ptr, n, arg, order_ptr, int(generation)), name)
+        return order
+
+    def _triangles(self, triangles):
+        """`triangles` as (the array kept alive, pointer, count, is_device): a contiguous (n, 18) float32 torch tensor on
+        the context's device (the caller waits for its stream, _stream_done), a numpy array of 72 bytes per triangle, or
+        a ctypes array of HalogenTriangle"""
+        if hasattr(triangles, "data_ptr") and not isinstance(triangles, np.ndarray):
+            return self._device_floats(triangles, 18, "triangles")
         if isinstance(triangles, np.ndarray):
             a = np.ascontiguousarray(triangles)
             if a.nbytes % C.sizeof(HalogenTriangle):
                 raise ValueError("triangles must hold 72 bytes per triangle")
-            n, keep = a.nbytes // C.sizeof(HalogenTriangle), a
-        else:
-            n, keep = len(triangles), triangles
-        order = np.zeros(n, dtype=np.int32)
-        self._check(getattr(lib(), name)(self._h, int(mesh_index), _ptr(keep), n, arg, _ptr(order), int(generation)),
-                    name)
-        return order
+            return a, _ptr(a), a.nbytes // C.sizeof(HalogenTriangle), False
+        return triangles, _ptr(triangles), len(triangles), False
+
+    @staticmethod
+    def _stream_done(tensor) -> None:
+        """Wait for torch's current stream on the tensor's device: what it holds is complete before the library reads it"""
+        import torch
+
+        torch.cuda.current_stream(tensor.device).synchronize()
 
     # --- deforming a mesh from its vertices (hg_set_mesh_vertices, hg_deform_mesh, hg_set_mesh_skin, hg_skin_mesh) ----
     def set_mesh_vertices(self, mesh_index: int, indices, n_vertices: int) -> None:
@@ -573,6 +571,25 @@ class Context:
         self._check(lib().hg_scene_readback(self._h, HG_SCENE_TRIS, None, 0, C.byref(n)), "hg_scene_readback")
         return (min(later) if later else n.value // 36) - start  # (the device keeps 9 floats a triangle)
 
+    def _order_buffer(self, mesh_index, kind, source, dev):
+        """(order, its pointer) for a deform of `kind` from `source`: a torch int32 tensor beside a device source (whose
+        stream is synchronised here: the source is complete before the call), a numpy int32 array otherwise; (None, None)
+        for a refit, which has no order"""
+        order = order_ptr = None
+        if kind != HG_DEFORM_REFIT:
+            n_tris = self._n_bound_triangles(mesh_index)
+            if dev:
+                import torch
+
+                order = torch.empty(n_tris, dtype=torch.int32, device=source.device)
+                order_ptr = C.c_void_p(order.data_ptr())
+            else:
+                order = np.zeros(n_tris, dtype=np.int32)
+                order_ptr = _ptr(order)
+        if dev:
+            self._stream_done(source)
+        return order, order_ptr
+
     def deform_mesh(self, mesh_index: int, positions, normals, how="refit", leaf_size: int = 0, node_cost: float = 0.0,
                     generation: int = 0):
         """Move mesh `mesh_index` (bound by set_mesh_vertices) to new vertex positions and normals, (n_vertices, 3) float32
@@ -587,21 +604,7 @@ class Context:
         q, qp, nq, dev_q = self._device_floats(normals, 3, "normals")
         if dev != dev_q or n != nq:
             raise ValueError("positions and normals must both be numpy arrays or both device tensors, of one length")
-        order = order_ptr = None
-        if kind != HG_DEFORM_REFIT:
-            n_tris = self._n_bound_triangles(mesh_index)
-            if dev:
-                import torch
-
-                order = torch.empty(n_tris, dtype=torch.int32, device=p.device)
-                order_ptr = C.c_void_p(order.data_ptr())
-            else:
-                order = np.zeros(n_tris, dtype=np.int32)
-                order_ptr = _ptr(order)
-        if dev:
-            import torch
-
-            torch.cuda.current_stream(p.device).synchronize()  # the vertices are complete before the call
+        order, order_ptr = self._order_buffer(mesh_index, kind, p, dev)
         name = "hg_deform_mesh_device" if dev else "hg_deform_mesh"
         self._check(getattr(lib(), name)(self._h, int(mesh_index), pp, qp, n, kind, int(leaf_size), float(node_cost),
                                          order_ptr, int(generation)), name)
@@ -630,21 +633,7 @@ class Context:
         arguments and the returned order are deform_mesh's."""
         kind = DEFORM_KINDS[how] if isinstance(how, str) else int(how)
         b, bp, n_bones, dev = self._device_floats(bones, 12, "bones")
-        order = order_ptr = None
-        if kind != HG_DEFORM_REFIT:
-            n_tris = self._n_bound_triangles(mesh_index)
-            if dev:
-                import torch
-
-                order = torch.empty(n_tris, dtype=torch.int32, device=b.device)
-                order_ptr = C.c_void_p(order.data_ptr())
-            else:
-                order = np.zeros(n_tris, dtype=np.int32)
-                order_ptr = _ptr(order)
-        if dev:
-            import torch
-
-            torch.cuda.current_stream(b.device).synchronize()  # the palette is complete before the call
+        order, order_ptr = self._order_buffer(mesh_index, kind, b, dev)
         name = "hg_skin_mesh_device" if dev else "hg_skin_mesh"
         self._check(getattr(lib(), name)(self._h, int(mesh_index), bp, n_bones, kind, int(leaf_size), float(node_cost),
                                          order_ptr, int(generation)), name)
