@@ -255,6 +255,15 @@ public static class HalogenNative
         [Out] float[] outNormals);
     [DllImport(Lib)] public static extern int hg_mesh_vertices_readback(IntPtr ctx, int meshIndex,
         [Out] float[] positions, [Out] float[] normals, int nVertices);
+    // Recomputed normals: HG_DEFORM_NORMALS, OR-ed into `how` of the four deform and skin calls above, takes the vertex
+    // normals from the moved faces on the device (area-weighted; `normals` may then be null) for a mesh bound by
+    // hg_set_mesh_vertices_opt with HG_BIND_ADJACENCY.  hg_vertex_normals is the host twin, bit for bit.
+    public const int HG_DEFORM_NORMALS = 0x100;
+    public const uint HG_BIND_ADJACENCY = 1;
+    [DllImport(Lib)] public static extern int hg_set_mesh_vertices_opt(IntPtr ctx, int meshIndex, int[] indices,
+        int nTriangles, int nVertices, uint flags);
+    [DllImport(Lib)] public static extern int hg_vertex_normals(float[] positions, int nVertices, int[] indices,
+        int nTriangles, [Out] float[] outNormals);
 
     // Multi-GPU gather (one context per GPU; the render pass keeps one HalogenRenderPass per device and gathers the
     // tiles to the display device once per displayed image).

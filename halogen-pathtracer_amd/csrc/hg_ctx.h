@@ -71,6 +71,12 @@ struct hg_ctx {
         DevBuf positions, normals;                                   // the skinned vertices
         int32_t n_bones = 0;  // 0: no skin
         bool skinned = false;  // positions / normals hold a pose
+        // hg_set_mesh_vertices_opt(HG_BIND_ADJACENCY), for HG_DEFORM_NORMALS (csrc/hg_normals.h): the list as it was
+        // bound, which no rebuild permutes; the inverted index over it (n_vertices + 1 offsets, 3 * n_tris face ids);
+        // the face pass's output (3 floats a triangle) and the vertex pass's for the deform forms (3 floats a vertex;
+        // the skin forms' goes to `normals`)
+        bool adjacency = false;
+        DevBuf frozen, adj_offsets, adj_faces, face_normals, vertex_normals;
     };
     std::map<uint32_t, VertexBinding> vertex_bindings;
     DevBuf deform_positions, deform_normals, deform_bones;  // the host-pointer forms' vertices and palette

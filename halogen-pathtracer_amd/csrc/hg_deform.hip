@@ -6,13 +6,18 @@
 // (vertex_source_check, before the tree's checks and before anything is launched) and the source as packed triangles
 // (vertex_source_device, after the quiesce), and goes on as for any other triangles.  Not in the reference.
 //
-// Three kernels, all on the context stream and ordered by it alone: no atomics, no kernel that waits on another
+// With HG_DEFORM_NORMALS the vertex normals are recomputed from the moved faces between the vertex source and the pack
+// (the contract: hg_normals.h; the host twin: hg_vertex_normals), through the adjacency hg_set_mesh_vertices_opt bound.
+//
+// Five kernels, all on the context stream and ordered by it alone: no atomics, no kernel that waits on another
 // workgroup.  The kernels first, then the two halves of a vertex source, then the entry points of the C-ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "halogen_abi.h"
+#include "hg_normals.h"
 #include "hg_rt.h"
 #include "hg_skin.h"
 #include "hg_tunables.h"
@@ -119,6 +124,60 @@ __global__ __launch_bounds__(kBlock) void hg_deform_permute(const int32_t* __res
     d[2] = c2;
 }
 
+// HG_DEFORM_NORMALS, first pass: out[t] = hg_face_normal of frozen[3t .. 3t + 2], 3 floats a triangle.  A workgroup takes
+// 256 triangles as hg_deform_pack does: its 768 indices are read by consecutive lanes, a lane per corner, whose position
+// (one scattered 12-byte read, the part a gather cannot avoid) goes to LDS; then a lane per triangle does the
+// arithmetic, and the 3 KiB of results leave as consecutive words.  Every index is below the vertex count
+// (hg_set_mesh_vertices_opt checked the list; nothing permutes the frozen copy).
+__global__ __launch_bounds__(kBlock) void hg_deform_face_normals(const int32_t* __restrict__ frozen, uint32_t n_tris,
+                                                                 const float* __restrict__ positions,
+                                                                 float* __restrict__ out) {
+    __shared__ float s_p[kBlock * 9];
+    __shared__ float s_f[kBlock * 3];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t base = blockIdx.x * uint32_t(kBlock);  // < n_tris: the grid is ceil(n_tris / 256)
+    const uint32_t cnt = min(uint32_t(kBlock), n_tris - base);
+    const int32_t* idx = frozen + size_t(base) * 3;
+    for (uint32_t i = tid; i < cnt * 3; i += kBlock) {
+        const size_t v = size_t(uint32_t(idx[i])) * 3;
+        s_p[i * 3] = positions[v];
+        s_p[i * 3 + 1] = positions[v + 1];
+        s_p[i * 3 + 2] = positions[v + 2];
+    }
+    __syncthreads();
+    if (tid < cnt) {
+        const float* p = s_p + tid * 9;
+        float f[3];
+        hg_face_normal(p, p + 3, p + 6, f);
+        for (int k = 0; k < 3; ++k) s_f[tid * 3 + k] = f[k];
+    }
+    __syncthreads();
+    float* g = out + size_t(base) * 3;
+    for (uint32_t i = tid; i < cnt * 3; i += kBlock) g[i] = s_f[i];
+}
+
+// HG_DEFORM_NORMALS, second pass: out[v] = hg_vertex_normal over the vertex's range of the adjacency, a lane per vertex:
+// the sum in the list's order, never split (a lane with a very long list runs long; its wave waits for it).  Every face id
+// is below the triangle count and the offsets ascend to 3 * n_tris (hg_normals_build_adjacency made them).  The
+// results leave through LDS as consecutive words.
+__global__ __launch_bounds__(kBlock) void hg_deform_vertex_normals(const int32_t* __restrict__ offsets,
+                                                                   const int32_t* __restrict__ faces,
+                                                                   const float* __restrict__ face_normals,
+                                                                   uint32_t n_vertices, float* __restrict__ out) {
+    __shared__ float s_n[kBlock * 3];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t base = blockIdx.x * uint32_t(kBlock);  // < n_vertices: the grid is ceil(n_vertices / 256)
+    const uint32_t cnt = min(uint32_t(kBlock), n_vertices - base);
+    if (tid < cnt) {
+        float n[3];
+        hg_vertex_normal(face_normals, faces, offsets[base + tid], offsets[base + tid + 1], n);
+        for (int k = 0; k < 3; ++k) s_n[tid * 3 + k] = n[k];
+    }
+    __syncthreads();
+    float* g = out + size_t(base) * 3;
+    for (uint32_t i = tid; i < cnt * 3; i += kBlock) g[i] = s_n[i];
+}
+
 // The scene, the mesh and its binding, for the entry point `who`
 int binding_of(hg_ctx* c, const char* who, int32_t mesh_index, hg_ctx::VertexBinding*& b) {
     if (!c->has_scene) return fail(c, HG_E_NOSCENE, "%s: hg_upload_scene not called", who);
@@ -148,7 +207,7 @@ namespace hgrt {
 
 void release_binding(hg_ctx::VertexBinding& b) {
     for (DevBuf* d : {&b.indices, &b.spare, &b.rest_positions, &b.rest_normals, &b.bone_indices, &b.weights, &b.positions,
-                      &b.normals})
+                      &b.normals, &b.frozen, &b.adj_offsets, &b.adj_faces, &b.face_normals, &b.vertex_normals})
         release(*d);
 }
 
@@ -163,11 +222,16 @@ int vertex_source_check(hg_ctx* c, const MeshUpdate& u, hg_ctx::VertexBinding*& 
             return fail(c, HG_E_INVALID, "%s: mesh %d: %d bones, its skin was bound with %d", u.who, u.mesh_index, u.count,
                         b->n_bones);
     } else {
-        if (!u.a || !u.b) return fail(c, HG_E_INVALID, "%s: null position or normal array", u.who);
+        if (u.recompute_normals ? !u.a : !u.a || !u.b)
+            return fail(c, HG_E_INVALID, "%s: null position%s array", u.who, u.recompute_normals ? "" : " or normal");
         if (u.count != b->n_vertices)
             return fail(c, HG_E_INVALID, "%s: mesh %d: %d vertices, its binding holds %d", u.who, u.mesh_index, u.count,
                         b->n_vertices);
     }
+    if (u.recompute_normals && !b->adjacency)
+        return fail(c, HG_E_INVALID,
+                    "%s: HG_DEFORM_NORMALS: mesh %d was bound without adjacency (hg_set_mesh_vertices_opt, HG_BIND_ADJACENCY)",
+                    u.who, u.mesh_index);
     if (u.how != HG_DEFORM_REFIT && u.how != HG_DEFORM_REBUILD && u.how != HG_DEFORM_REBUILD_SAH)
         return fail(c, HG_E_INVALID, "%s: unknown kind of deform %d", u.who, u.how);
     return HG_OK;
@@ -201,7 +265,21 @@ int vertex_source_device(hg_ctx* c, const MeshUpdate& u, hg_ctx::VertexBinding& 
     } else {
         const size_t bytes = size_t(u.count) * 3 * sizeof(float);
         if (int rc = on_device(c, u, u.a, c->deform_positions, bytes, d_positions)) return rc;
-        if (int rc = on_device(c, u, u.b, c->deform_normals, bytes, d_normals)) return rc;
+        if (!u.recompute_normals)
+            if (int rc = on_device(c, u, u.b, c->deform_normals, bytes, d_normals)) return rc;
+    }
+    if (u.recompute_normals) {  // the normals from the moved faces: the face pass, then the vertex pass (hg_normals.h)
+        float* out = static_cast<float*>(u.source == MeshUpdate::kBones ? b.normals.p : b.vertex_normals.p);
+        hipLaunchKernelGGL(hg_deform_face_normals, dim3(uint32_t((b.n_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                           c->stream, static_cast<const int32_t*>(b.frozen.p), uint32_t(b.n_tris),
+                           static_cast<const float*>(d_positions), static_cast<float*>(b.face_normals.p));
+        HG_HIP(c, hipGetLastError());
+        hipLaunchKernelGGL(hg_deform_vertex_normals, dim3(uint32_t((b.n_vertices + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                           c->stream, static_cast<const int32_t*>(b.adj_offsets.p),
+                           static_cast<const int32_t*>(b.adj_faces.p), static_cast<const float*>(b.face_normals.p),
+                           uint32_t(b.n_vertices), out);
+        HG_HIP(c, hipGetLastError());
+        d_normals = out;
     }
     hipLaunchKernelGGL(hg_deform_pack, dim3(uint32_t((b.n_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
                        static_cast<const int32_t*>(b.indices.p), uint32_t(b.n_tris), static_cast<const float*>(d_positions),
@@ -226,10 +304,11 @@ int deform_follow_order(hg_ctx* c, uint32_t tri_offset, const uint32_t* d_order,
 
 }  // namespace hgrt
 
-extern "C" {
+namespace {
 
-int hg_set_mesh_vertices(hg_ctx* c, int32_t mesh_index, const int32_t* indices, int32_t n_tris, int32_t n_vertices) {
-    static const char* who = "hg_set_mesh_vertices";
+// hg_set_mesh_vertices (flags 0) and hg_set_mesh_vertices_opt
+int bind_vertices(hg_ctx* c, const char* who, int32_t mesh_index, const int32_t* indices, int32_t n_tris,
+                  int32_t n_vertices, uint32_t flags) {
     if (!c) return HG_E_INVALID;
     if (int rc = hg_ctx_flush(c)) return rc;
     if (c->has_scene && !indices) return fail(c, HG_E_INVALID, "%s: null index array", who);
@@ -245,6 +324,12 @@ int hg_set_mesh_vertices(hg_ctx* c, int32_t mesh_index, const int32_t* indices, 
     if (bad >= 0)
         return fail(c, HG_E_INVALID, "%s: mesh %d: index %d of triangle %lld is outside the %d vertices", who, mesh_index,
                     indices[bad], static_cast<long long>(bad / 3), n_vertices);
+    if (flags & ~uint32_t(HG_BIND_ADJACENCY))
+        return fail(c, HG_E_INVALID, "%s: unknown flags 0x%x", who, flags & ~uint32_t(HG_BIND_ADJACENCY));
+    const bool adjacency = (flags & HG_BIND_ADJACENCY) != 0;
+    if (adjacency && n_tris > HG_NORMALS_MAX_TRIANGLES)
+        return fail(c, HG_E_INVALID, "%s: mesh %d: an adjacency holds at most %d triangles", who, mesh_index,
+                    HG_NORMALS_MAX_TRIANGLES);
     if (int rc = set_device(c)) return rc;
     const uint32_t key = c->dev_meshes[size_t(mesh_index)].tri_offset;
     auto old = c->vertex_bindings.find(key);
@@ -255,24 +340,64 @@ int hg_set_mesh_vertices(hg_ctx* c, int32_t mesh_index, const int32_t* indices, 
     }
     hg_ctx::VertexBinding b;
     if (int rc = upload(c, b.indices, indices, size_t(n_tris) * 3 * sizeof(int32_t))) return rc;
-    HG_HIP(c, hipStreamSynchronize(c->stream));  // the caller's array is free again
+    std::vector<int32_t> offsets, faces;  // (alive until the stream has taken them)
+    if (adjacency) {
+        offsets.resize(size_t(n_vertices) + 1);
+        faces.resize(size_t(n_tris) * 3);
+        hg_normals_build_adjacency(indices, n_tris, n_vertices, offsets.data(), faces.data());
+        int rc;
+        if ((rc = upload(c, b.frozen, indices, size_t(n_tris) * 3 * sizeof(int32_t))) ||
+            (rc = upload(c, b.adj_offsets, offsets.data(), offsets.size() * sizeof(int32_t))) ||
+            (rc = upload(c, b.adj_faces, faces.data(), faces.size() * sizeof(int32_t))) ||
+            (rc = ensure(c, b.face_normals, size_t(n_tris) * 3 * sizeof(float))) ||
+            (rc = ensure(c, b.vertex_normals, size_t(n_vertices) * 3 * sizeof(float)))) {
+            (void)hipStreamSynchronize(c->stream);  // (no copy in flight reads a freed buffer)
+            release_binding(b);
+            return rc;
+        }
+        b.adjacency = true;
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);  // the caller's array is free again
+    if (e != hipSuccess) {
+        release_binding(b);
+        return fail(c, HG_E_HIP, "%s failed: %s", "hipStreamSynchronize(c->stream)", hipGetErrorString(e));
+    }
     b.n_tris = n_tris;
     b.n_vertices = n_vertices;
     c->vertex_bindings[key] = b;
     return HG_OK;
 }
 
+// `how` of the deform and skin entry points without HG_DEFORM_NORMALS, and the flag
+int kind_of(int32_t how) { return how & ~int32_t(HG_DEFORM_NORMALS); }
+bool normals_of(int32_t how) { return (how & HG_DEFORM_NORMALS) != 0; }
+
+}  // namespace
+
+extern "C" {
+
+int hg_set_mesh_vertices(hg_ctx* c, int32_t mesh_index, const int32_t* indices, int32_t n_tris, int32_t n_vertices) {
+    return bind_vertices(c, "hg_set_mesh_vertices", mesh_index, indices, n_tris, n_vertices, 0);
+}
+
+int hg_set_mesh_vertices_opt(hg_ctx* c, int32_t mesh_index, const int32_t* indices, int32_t n_tris, int32_t n_vertices,
+                             uint32_t flags) {
+    return bind_vertices(c, "hg_set_mesh_vertices_opt", mesh_index, indices, n_tris, n_vertices, flags);
+}
+
 int hg_deform_mesh_device(hg_ctx* c, int32_t mesh_index, const void* d_positions, const void* d_normals,
                           int32_t n_vertices, int32_t how, int32_t leaf_size, float node_cost, void* d_order,
                           uint64_t geometry_generation) {
-    return update_mesh(c, {"hg_deform_mesh_device", mesh_index, MeshUpdate::kVertices, d_positions, d_normals, n_vertices,
-                           true, how, leaf_size, node_cost, d_order, geometry_generation});
+    return update_mesh(c, {"hg_deform_mesh_device", mesh_index, MeshUpdate::kVertices, d_positions,
+                           normals_of(how) ? nullptr : d_normals, n_vertices, true, kind_of(how), leaf_size, node_cost,
+                           d_order, geometry_generation, normals_of(how)});
 }
 
 int hg_deform_mesh(hg_ctx* c, int32_t mesh_index, const float* positions, const float* normals, int32_t n_vertices,
                    int32_t how, int32_t leaf_size, float node_cost, int32_t* order, uint64_t geometry_generation) {
-    return update_mesh(c, {"hg_deform_mesh", mesh_index, MeshUpdate::kVertices, positions, normals, n_vertices, false, how,
-                           leaf_size, node_cost, order, geometry_generation});
+    return update_mesh(c, {"hg_deform_mesh", mesh_index, MeshUpdate::kVertices, positions, normals_of(how) ? nullptr : normals,
+                           n_vertices, false, kind_of(how), leaf_size, node_cost, order, geometry_generation,
+                           normals_of(how)});
 }
 
 int hg_set_mesh_skin(hg_ctx* c, int32_t mesh_index, const float* rest_positions, const float* rest_normals,
@@ -310,14 +435,14 @@ int hg_set_mesh_skin(hg_ctx* c, int32_t mesh_index, const float* rest_positions,
 
 int hg_skin_mesh_device(hg_ctx* c, int32_t mesh_index, const void* d_bones, int32_t n_bones, int32_t how,
                         int32_t leaf_size, float node_cost, void* d_order, uint64_t geometry_generation) {
-    return update_mesh(c, {"hg_skin_mesh_device", mesh_index, MeshUpdate::kBones, d_bones, nullptr, n_bones, true, how,
-                           leaf_size, node_cost, d_order, geometry_generation});
+    return update_mesh(c, {"hg_skin_mesh_device", mesh_index, MeshUpdate::kBones, d_bones, nullptr, n_bones, true,
+                           kind_of(how), leaf_size, node_cost, d_order, geometry_generation, normals_of(how)});
 }
 
 int hg_skin_mesh(hg_ctx* c, int32_t mesh_index, const float* bones, int32_t n_bones, int32_t how, int32_t leaf_size,
                  float node_cost, int32_t* order, uint64_t geometry_generation) {
-    return update_mesh(c, {"hg_skin_mesh", mesh_index, MeshUpdate::kBones, bones, nullptr, n_bones, false, how, leaf_size,
-                           node_cost, order, geometry_generation});
+    return update_mesh(c, {"hg_skin_mesh", mesh_index, MeshUpdate::kBones, bones, nullptr, n_bones, false, kind_of(how),
+                           leaf_size, node_cost, order, geometry_generation, normals_of(how)});
 }
 
 int hg_mesh_vertices_readback(hg_ctx* c, int32_t mesh_index, float* positions, float* normals, int32_t n_vertices) {

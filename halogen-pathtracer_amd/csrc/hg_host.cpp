@@ -27,6 +27,7 @@
 #include "hg_atrous.h"
 #include "hg_host_pool.h"
 #include "hg_lbvh.h"
+#include "hg_normals.h"
 #include "hg_refit.h"
 #include "hg_skin.h"
 
@@ -539,6 +540,25 @@ extern "C" int hg_skin_vertices(const float* rest_positions, const float* rest_n
     for (int64_t v = 0; v < n_vertices; ++v)
         hg_skin_vertex(bones, bone_indices + 4 * v, weights + 4 * v, rest_positions + 3 * v, rest_normals + 3 * v,
                        out_positions + 3 * v, out_normals + 3 * v);
+    return HG_OK;
+}
+
+// hg_vertex_normals: the host twin of a deform with HG_DEFORM_NORMALS (hg_deform.hip), over the contract of
+// hg_normals.h: the adjacency, every face's normal, every vertex's sum through the adjacency.  Everything is validated
+// before the first normal is written.
+extern "C" int hg_vertex_normals(const float* positions, int32_t n_vertices, const int32_t* indices, int32_t n_triangles,
+                                 float* out_normals) {
+    if (!positions || !indices || !out_normals) return HG_E_INVALID;
+    if (n_vertices < 1 || n_triangles < 1 || n_triangles > HG_NORMALS_MAX_TRIANGLES) return HG_E_INVALID;
+    if (hg_skin_first_bad_index(indices, n_triangles, n_vertices) >= 0) return HG_E_INVALID;
+    std::vector<int32_t> offsets(size_t(n_vertices) + 1), faces(size_t(n_triangles) * 3);
+    hg_normals_build_adjacency(indices, n_triangles, n_vertices, offsets.data(), faces.data());
+    std::vector<float> face_normals(size_t(n_triangles) * 3);
+    for (int64_t t = 0; t < n_triangles; ++t)
+        hg_face_normal(positions + size_t(indices[3 * t]) * 3, positions + size_t(indices[3 * t + 1]) * 3,
+                       positions + size_t(indices[3 * t + 2]) * 3, face_normals.data() + 3 * t);
+    for (int64_t v = 0; v < n_vertices; ++v)
+        hg_vertex_normal(face_normals.data(), faces.data(), offsets[size_t(v)], offsets[size_t(v) + 1], out_normals + 3 * v);
     return HG_OK;
 }
 

@@ -92,11 +92,13 @@ struct MeshUpdate {
     const void* b;  // nullptr                   | vertex normals   | nullptr
     int32_t count;
     bool device;    // a, b and order are device pointers (else host pointers)
-    int32_t how;    // HG_DEFORM_REFIT, HG_DEFORM_REBUILD (leaf_size) or HG_DEFORM_REBUILD_SAH (node_cost)
+    int32_t how;    // HG_DEFORM_REFIT, HG_DEFORM_REBUILD (leaf_size) or HG_DEFORM_REBUILD_SAH (node_cost); no flag bits
     int32_t leaf_size;
     float node_cost;
     void* order;  // optional: where a rebuild's order goes
     uint64_t generation;
+    // HG_DEFORM_NORMALS (vertices, bones): the vertex normals are recomputed from the moved faces; b is nullptr
+    bool recompute_normals = false;
 };
 // The one path of them all (hg_refit.hip; its header has the steps)
 int update_mesh(hg_ctx* c, const MeshUpdate& u);

@@ -164,10 +164,13 @@ EXPORTS = [
     "hg_build_blas_lbvh_sah", "hg_rebuild_mesh_sah", "hg_rebuild_mesh_sah_device",
     "hg_set_mesh_vertices", "hg_deform_mesh", "hg_deform_mesh_device", "hg_set_mesh_skin", "hg_skin_mesh",
     "hg_skin_mesh_device", "hg_skin_vertices", "hg_mesh_vertices_readback",
+    "hg_set_mesh_vertices_opt", "hg_vertex_normals",
 ]
 # hg_deform_mesh / hg_skin_mesh: what follows the pack (Context.deform_mesh(how=...))
 HG_DEFORM_REFIT, HG_DEFORM_REBUILD, HG_DEFORM_REBUILD_SAH = 0, 1, 2
 DEFORM_KINDS = {"refit": HG_DEFORM_REFIT, "lbvh": HG_DEFORM_REBUILD, "sah": HG_DEFORM_REBUILD_SAH}
+HG_DEFORM_NORMALS = 0x100  # OR-ed into `how`: the vertex normals are recomputed on the device (recompute_normals=True)
+HG_BIND_ADJACENCY = 1  # hg_set_mesh_vertices_opt: what HG_DEFORM_NORMALS needs (set_mesh_vertices(adjacency=True))
 HG_SKIN_LDS_BONES = 256  # csrc/hg_tunables.h: the largest bone palette the skin kernel keeps in LDS
 # hg_scene_readback: the device scene's arrays (layouts private to the library, csrc/hg_layout.h)
 HG_SCENE_NODES, HG_SCENE_LEAVES, HG_SCENE_TRIS, HG_SCENE_NORMALS, HG_SCENE_MESHES = 0, 1, 2, 3, 4
@@ -263,6 +266,8 @@ def lib() -> C.CDLL:
         "hg_skin_mesh_device": (C.c_int, [P, i32, P, i32, i32, i32, C.c_float, P, C.c_uint64]),
         "hg_skin_vertices": (C.c_int, [P, P, P, P, i32, P, i32, P, P]),
         "hg_mesh_vertices_readback": (C.c_int, [P, i32, P, P, i32]),
+        "hg_set_mesh_vertices_opt": (C.c_int, [P, i32, P, i32, i32, C.c_uint32]),
+        "hg_vertex_normals": (C.c_int, [P, i32, P, i32, P]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -538,13 +543,21 @@ class Context:
         torch.cuda.current_stream(tensor.device).synchronize()
 
     # --- deforming a mesh from its vertices (hg_set_mesh_vertices, hg_deform_mesh, hg_set_mesh_skin, hg_skin_mesh) ----
-    def set_mesh_vertices(self, mesh_index: int, indices, n_vertices: int) -> None:
+    def set_mesh_vertices(self, mesh_index: int, indices, n_vertices: int, adjacency: bool = False, flags=None) -> None:
         """Bind the index list of mesh `mesh_index` ((n, 3) integers: its triangles in their current order, as they were
         uploaded) to its tree on the device, for deform_mesh / skin_mesh.  The library keeps the list in step with every
-        later rebuild of the tree; the binding lives until the next full upload of the scene."""
+        later rebuild of the tree; the binding lives until the next full upload of the scene.  adjacency=True
+        (hg_set_mesh_vertices_opt, HG_BIND_ADJACENCY) also binds what recompute_normals=True of those calls needs: the
+        vertices' face lists, built here on the host, and room for the normals.  `flags`: the call's flags as given."""
         idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
-        self._check(lib().hg_set_mesh_vertices(self._h, int(mesh_index), _ptr(idx) if idx.size else None, idx.shape[0],
-                                               int(n_vertices)), "hg_set_mesh_vertices")
+        ip = _ptr(idx) if idx.size else None
+        if not adjacency and flags is None:
+            self._check(lib().hg_set_mesh_vertices(self._h, int(mesh_index), ip, idx.shape[0], int(n_vertices)),
+                        "hg_set_mesh_vertices")
+            return
+        f = int(flags) if flags is not None else HG_BIND_ADJACENCY
+        self._check(lib().hg_set_mesh_vertices_opt(self._h, int(mesh_index), ip, idx.shape[0], int(n_vertices), f),
+                    "hg_set_mesh_vertices_opt")
 
     def _device_floats(self, a, cols, what):
         """`a` as (the array kept alive, pointer, rows, is_device): a contiguous (rows, cols) float32 torch tensor on the context's device
@@ -590,21 +603,26 @@ class Context:
             self._stream_done(source)
         return order, order_ptr
 
-    def deform_mesh(self, mesh_index: int, positions, normals, how="refit", leaf_size: int = 0, node_cost: float = 0.0,
-                    generation: int = 0):
+    def deform_mesh(self, mesh_index: int, positions, normals=None, how="refit", leaf_size: int = 0,
+                    node_cost: float = 0.0, generation: int = 0, recompute_normals: bool = False):
         """Move mesh `mesh_index` (bound by set_mesh_vertices) to new vertex positions and normals, (n_vertices, 3) float32
         each: the triangles are packed on the device from the bound index list, then the mesh's tree is refitted
         (how="refit": refit_mesh), rebuilt as a linear BVH (how="lbvh", leaf_size: rebuild_mesh) or rebuilt with leaves
         chosen by surface area (how="sah", node_cost: rebuild_mesh_sah).  Both arrays on the host (numpy), or both
         contiguous float32 torch tensors on the context's device, read in place.  The rebuild kinds return the new
         order as rebuild_mesh does (a torch int32 tensor for tensors, a numpy int32 array otherwise); "refit" returns
-        None."""
+        None.  recompute_normals=True (HG_DEFORM_NORMALS; a binding with adjacency=True): the normals are recomputed
+        on the device from the moved faces, vertex_normals' bits; `normals` is ignored and may be None."""
         kind = DEFORM_KINDS[how] if isinstance(how, str) else int(how)
         p, pp, n, dev = self._device_floats(positions, 3, "positions")
-        q, qp, nq, dev_q = self._device_floats(normals, 3, "normals")
-        if dev != dev_q or n != nq:
-            raise ValueError("positions and normals must both be numpy arrays or both device tensors, of one length")
-        order, order_ptr = self._order_buffer(mesh_index, kind, p, dev)
+        q = qp = None
+        if recompute_normals:
+            kind |= HG_DEFORM_NORMALS
+        elif normals is not None:
+            q, qp, nq, dev_q = self._device_floats(normals, 3, "normals")
+            if dev != dev_q or n != nq:
+                raise ValueError("positions and normals must both be numpy arrays or both device tensors, of one length")
+        order, order_ptr = self._order_buffer(mesh_index, kind & ~HG_DEFORM_NORMALS, p, dev)
         name = "hg_deform_mesh_device" if dev else "hg_deform_mesh"
         self._check(getattr(lib(), name)(self._h, int(mesh_index), pp, qp, n, kind, int(leaf_size), float(node_cost),
                                          order_ptr, int(generation)), name)
@@ -626,14 +644,17 @@ class Context:
                                            int(n_bones)), "hg_set_mesh_skin")
 
     def skin_mesh(self, mesh_index: int, bones, how="refit", leaf_size: int = 0, node_cost: float = 0.0,
-                  generation: int = 0):
+                  generation: int = 0, recompute_normals: bool = False):
         """Pose a skinned mesh (set_mesh_skin) by a bone palette, (n_bones, 12) float32: row-major 3 x 4 matrices, on the
         host or as a contiguous torch tensor on the context's device.  The vertices are skinned on the device
         (linear blend, abi.skin_vertices' arithmetic bit for bit) and then go the way of deform_mesh; `how`, the other
-        arguments and the returned order are deform_mesh's."""
+        arguments and the returned order are deform_mesh's.  recompute_normals=True: the skinned normals are replaced
+        by those recomputed from the skinned positions (right for any bones, non-uniformly scaled ones too)."""
         kind = DEFORM_KINDS[how] if isinstance(how, str) else int(how)
+        if recompute_normals:
+            kind |= HG_DEFORM_NORMALS
         b, bp, n_bones, dev = self._device_floats(bones, 12, "bones")
-        order, order_ptr = self._order_buffer(mesh_index, kind, b, dev)
+        order, order_ptr = self._order_buffer(mesh_index, kind & ~HG_DEFORM_NORMALS, b, dev)
         name = "hg_skin_mesh_device" if dev else "hg_skin_mesh"
         self._check(getattr(lib(), name)(self._h, int(mesh_index), bp, n_bones, kind, int(leaf_size), float(node_cost),
                                          order_ptr, int(generation)), name)
@@ -820,6 +841,22 @@ def refit_blas(triangles, nodes) -> None:
     rc = lib().hg_refit_blas(_ptr(triangles), len(triangles), _ptr(nodes), len(nodes))
     if rc != HG_OK:
         raise HalogenError(f"hg_refit_blas failed ({rc}): a range, the depth or a cycle of the tree", rc)
+
+
+def vertex_normals(positions, indices) -> np.ndarray:
+    """hg_vertex_normals, the host twin of deform_mesh / skin_mesh with recompute_normals=True: area-weighted vertex
+    normals of (n, 3) positions under an (m, 3) index list, each vertex's faces summed in the order of their index
+    triples (csrc/hg_normals.h), so the result does not depend on the order of the list; (0, 0, 0) for a vertex no
+    triangle with an area names.  Returns (n, 3) float32.  Needs no GPU."""
+    p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
+    out = np.empty_like(p)
+    rc = lib().hg_vertex_normals(_ptr(p) if p.size else None, len(p), _ptr(idx) if idx.size else None, len(idx),
+                                 _ptr(out) if out.size else None)
+    if rc != HG_OK:
+        raise HalogenError(f"hg_vertex_normals failed ({rc}): no vertices, no triangles, or an index outside the "
+                           f"{len(p)} vertices", rc)
+    return out
 
 
 def skin_vertices(rest_positions, rest_normals, bone_indices, weights, bones):

@@ -160,12 +160,18 @@ class HalogenRenderPass:
     """Progressive path tracing of a `halogen.scene.Scene` on one GPU (or one rank's tiles)."""
 
     def __init__(self, settings: HalogenSettings, device: int = 0, context: abi.Context | None = None,
-                 vertex_deform: bool = False):
+                 vertex_deform: bool = False, recompute_normals: bool = False):
         self.settings = settings
         # opt-in: after every full upload the pass binds each mesh's index list to the device (Context.set_mesh_vertices)
         # and sends a deformed mesh's vertices and normals (24 B a vertex, packed on the device: Context.deform_mesh)
         # where it otherwise sends the packed triangles (72 B a triangle: Context.refit_mesh).  The same device scene.
         self.vertex_deform = bool(vertex_deform)
+        # with vertex_deform: the lists are bound with their adjacency, and a mesh whose last deform took its normals from
+        # the moved faces (deform(..., normals="recompute")) sends its positions alone (12 B a vertex): the device
+        # recomputes the same normals (Context.deform_mesh(recompute_normals=True)).  The same device scene again.
+        if recompute_normals and not vertex_deform:
+            raise ValueError("recompute_normals needs vertex_deform")
+        self.recompute_normals = bool(recompute_normals)
         self.s = clamp_settings(settings)
         self.ctx = context if context is not None else abi.Context(device)
         # the pass never reads the work counters (the reference has none); off, the render server may trace the next
@@ -254,7 +260,7 @@ class HalogenRenderPass:
         if bind:
             for i, m in enumerate(scene.meshes):
                 if m.triangle_count:
-                    self.ctx.set_mesh_vertices(i, m.triangles, len(m.vertices))
+                    self.ctx.set_mesh_vertices(i, m.triangles, len(m.vertices), adjacency=self.recompute_normals)
         self._guides_dirty = True
         self._scene_counts = (len(packed.spheres), len(packed.meshes))
         cube = self.settings.environmentCubemap
@@ -266,7 +272,9 @@ class HalogenRenderPass:
     def _refit(self, i, m):
         """The device refit of a deformed mesh under the current generation: from its vertices (vertex_deform; a rebuild
         on the device has kept the bound index list in the mesh's order) or from its packed triangles"""
-        if self.vertex_deform:
+        if self.vertex_deform and self.recompute_normals and m.normals_recomputed:
+            self.ctx.deform_mesh(i, m.vertices, None, generation=self._geometry[1], recompute_normals=True)
+        elif self.vertex_deform:
             self.ctx.deform_mesh(i, m.vertices, m.normals, generation=self._geometry[1])
         else:
             self.ctx.refit_mesh(i, m.packed_triangles, self._geometry[1])

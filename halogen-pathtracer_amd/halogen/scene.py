@@ -121,6 +121,7 @@ class RayTracingMesh:
         # is the device's until the pass rebuilds), its leaf size, and deform_serial right after it
         self.rebuild_serial, self.rebuild_input, self.rebuild_leaf, self.rebuild_at = 0, None, 0, 0
         self.rebuild_node_cost = None  # of a deform(rebuild="sah"): the node cost its twin used
+        self.normals_recomputed = False  # the last deform() took normals="recompute"
         self._cache()
 
     def _cache(self):
@@ -175,9 +176,21 @@ class RayTracingMesh:
 
         rebuild="sah" is the rebuild with leaves chosen by surface area (abi.build_blas_lbvh_sah, the host twin of
         Context.rebuild_mesh_sah) at node_cost (0: the library's value, doubled until the tree fits), under the same
-        rule of fit; rebuild_node_cost keeps the cost the twin used, which is what the pass gives the device."""
+        rule of fit; rebuild_node_cost keeps the cost the twin used, which is what the pass gives the device.
+
+        normals="recompute" takes the normals from the moved faces (abi.vertex_normals, the host twin of
+        Context.deform_mesh(recompute_normals=True): area-weighted, independent of the triangles' order);
+        normals_recomputed remembers it, and a pass with recompute_normals then sends the positions alone."""
         v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
-        n = self.normals if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        recompute = isinstance(normals, str)
+        if recompute:
+            if normals != "recompute":
+                raise ValueError(f"normals must be an array, None or 'recompute', not {normals!r}")
+            if v.shape != self.vertices.shape:
+                raise ValueError("deform keeps the vertex count")
+            n = abi.vertex_normals(v, self.triangles) if len(self.triangles) else np.zeros_like(v)
+        else:
+            n = self.normals if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
         if v.shape != self.vertices.shape or n.shape != v.shape:
             raise ValueError("deform keeps the vertex count")
         fit = []
@@ -207,6 +220,7 @@ class RayTracingMesh:
                 raise ValueError(f"{self.name}: no LBVH with leaf size {leaf_size or '4..15'} fits the {self.bvh_inner} "
                                  f"inner entries of its tree")
         self.vertices, self.normals = v, n
+        self.normals_recomputed = recompute
         rc = abi.lib().hg_pack_triangles(v.ctypes.data, n.ctypes.data, len(v), self.triangles.ctypes.data,
                                          len(self.triangles), C.cast(self.packed_triangles, C.c_void_p))
         if rc != 0:
@@ -245,14 +259,17 @@ class RayTracingMesh:
         self.rest_vertices, self.rest_normals = self.vertices.copy(), self.normals.copy()
         self.bone_indices, self.bone_weights = b, w
 
-    def pose(self, bones, rebuild=False, leaf_size: int = 0, node_cost: float = 0.0) -> None:
+    def pose(self, bones, rebuild=False, leaf_size: int = 0, node_cost: float = 0.0, normals=None) -> None:
         """Pose the skinned mesh (set_skin) by a bone palette, (n_bones, 12) row-major 3 x 4 matrices: the rest pose goes
         through abi.skin_vertices (the host twin of Context.skin_mesh) and the result through deform() as it is, so the
-        host arrays stay current.  rebuild, leaf_size, node_cost: deform's."""
+        host arrays stay current.  rebuild, leaf_size, node_cost: deform's.  normals="recompute": the skinned normals are
+        replaced by those of the skinned faces (the twin of Context.skin_mesh(recompute_normals=True))."""
         if getattr(self, "bone_indices", None) is None:
             raise ValueError(f"{self.name}: pose needs set_skin")
         v, n = abi.skin_vertices(self.rest_vertices, self.rest_normals, self.bone_indices, self.bone_weights, bones)
-        self.deform(v, n, rebuild=rebuild, leaf_size=leaf_size, node_cost=node_cost)
+        if normals is not None and not (isinstance(normals, str) and normals == "recompute"):
+            raise ValueError(f"normals must be None or 'recompute', not {normals!r}")
+        self.deform(v, n if normals is None else normals, rebuild=rebuild, leaf_size=leaf_size, node_cost=node_cost)
 
     @property
     def triangle_count(self) -> int:

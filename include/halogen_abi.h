@@ -468,9 +468,9 @@ int hg_rebuild_mesh_sah_device(hg_ctx* ctx, int32_t mesh_index, const void* d_tr
  *   HG_DEFORM_REBUILD_SAH  hg_rebuild_mesh_sah_device (uses node_cost)
  * does: flush, quiesce, guide images, accumulation, generation, upload rule, capacity, `order` and refusals are
  * theirs.  Also refused (HG_E_INVALID): a mesh without a binding; n_vertices other than the bound count; a null
- * position or normal array; an unknown `how`; a misaligned device pointer.  The normals are the caller's: recomputing
- * vertex normals from the moved faces is out of scope, and so are morph-target blending (blend the vertices, then call
- * this) and growing a tree's record capacity.
+ * position or normal array; an unknown `how`; a misaligned device pointer.  The normals are the caller's unless
+ * HG_DEFORM_NORMALS asks for them (below).  Out of scope: morph-target blending (blend the vertices, then call this)
+ * and growing a tree's record capacity.
  * The caller's duty afterwards is a refit's: its own host arrays must be current before any later full upload
  * (hg_skin_vertices, hg_pack_triangles and hg_refit_blas or the rebuild twins give it that).
  *
@@ -488,10 +488,37 @@ int hg_rebuild_mesh_sah_device(hg_ctx* ctx, int32_t mesh_index, const void* d_tr
  * written: a null array, n_vertices < 1, n_bones outside 1..65536, a bone index not below n_bones.
  * hg_mesh_vertices_readback: a diagnostic copy of the vertices the last hg_skin_mesh* of the mesh produced (either
  * pointer may be NULL), in the spirit of hg_scene_readback.
+ *
+ * RECOMPUTED NORMALS, for a caller who holds moved positions and nothing else (a cloth step, a morph blend, bones that
+ * scale non-uniformly).  The contract is csrc/hg_normals.h's, fp32 in a stated order: a face's normal is the cross
+ * product (b - a) x (c - a) of its corners, unnormalised, so faces weigh by area; a vertex's normal is the sum of the
+ * normals of the corners that name it, taken in ascending order of the triangles' index triples, normalised where its
+ * squared length is > 0 and (0, 0, 0) otherwise (an unreferenced vertex, only zero-area faces).  The order by triple
+ * makes the result a function of the positions and the SET of triangles, not of their order, which rebuilds change.
+ * hg_vertex_normals: the host twin (no device work).  HG_E_INVALID, with nothing written: a null array, n_vertices < 1,
+ * n_triangles < 1 (or above INT32_MAX / 3), an index outside [0, n_vertices).
+ * hg_set_mesh_vertices_opt is hg_set_mesh_vertices (which is this call with flags 0) with `flags`.  HG_BIND_ADJACENCY:
+ * the binding also keeps, on the device and until it is released, a copy of the list as bound that no rebuild permutes
+ * (12 bytes a triangle), the inverted index over it (4 bytes a vertex and 4 a corner, built on the host in this call),
+ * and room for the face normals (12 bytes a triangle) and the vertex normals (12 bytes a vertex).  Checks, refusals
+ * and lifetime are hg_set_mesh_vertices's; an unknown flag bit is HG_E_INVALID; rebinding without the flag drops the
+ * adjacency.
+ * HG_DEFORM_NORMALS, OR-ed into `how` of hg_deform_mesh, hg_deform_mesh_device, hg_skin_mesh and hg_skin_mesh_device:
+ * the normals are recomputed on the device from the moved positions, bit for bit hg_vertex_normals', in two kernels
+ * between the vertex source and the pack (no atomics: every face's normal is stored, then every vertex sums its own
+ * list).  The deform forms then ignore `normals`, which may be NULL; the skin forms replace the skinned normals, and
+ * hg_mesh_vertices_readback returns the recomputed ones.  Refused (HG_E_INVALID, nothing launched): a binding made
+ * without HG_BIND_ADJACENCY.  Out of scope: angle weighting (its acos does not round alike on host and device) and
+ * splitting a long adjacency list among lanes (it would change the order of the sum).
  * -------------------------------------------------------------------------------------------- */
-enum { HG_DEFORM_REFIT = 0, HG_DEFORM_REBUILD = 1, HG_DEFORM_REBUILD_SAH = 2 };
+enum { HG_DEFORM_REFIT = 0, HG_DEFORM_REBUILD = 1, HG_DEFORM_REBUILD_SAH = 2, HG_DEFORM_NORMALS = 0x100 };
+enum { HG_BIND_ADJACENCY = 1 };
 int hg_set_mesh_vertices(hg_ctx* ctx, int32_t mesh_index, const int32_t* indices, int32_t n_triangles,
                          int32_t n_vertices);
+int hg_set_mesh_vertices_opt(hg_ctx* ctx, int32_t mesh_index, const int32_t* indices, int32_t n_triangles,
+                             int32_t n_vertices, uint32_t flags);
+int hg_vertex_normals(const float* positions, int32_t n_vertices, const int32_t* indices, int32_t n_triangles,
+                      float* out_normals);
 int hg_deform_mesh(hg_ctx* ctx, int32_t mesh_index, const float* positions, const float* normals, int32_t n_vertices,
                    int32_t how, int32_t leaf_size, float node_cost, int32_t* order, uint64_t geometry_generation);
 int hg_deform_mesh_device(hg_ctx* ctx, int32_t mesh_index, const void* d_positions, const void* d_normals,
