@@ -4,7 +4,8 @@
 // compile to without it.
 #include <hip/hip_runtime.h>
 
-#include "hg_device.h"
+#include "hg_dev_records.h"
+#include "hg_dev_wave.h"
 #include "hg_launch.h"
 
 using namespace hgd;

@@ -44,12 +44,7 @@ __global__ __launch_bounds__(kGuideBlock, HG_GUIDE_WAVES) void hg_guides_kernel(
         t_max = HG_INF;
     }
     const MegaStack stk{threadIdx.x, uint32_t(kGuideBlock), kp.spill + k, kp.spill_stride};
-    Hit h;
-    h.t = t_max;
-    h.orient = 0.0f;
-    h.pos = mk(0, 0, 0);
-    h.n = mk(0, 0, 0);
-    h.mat = 0;
+    Hit h = hit_none(t_max);
     const uint32_t sph = isect_spheres(kp, ray, h.t);
     MeshBest mb{0.0f, 0.0f, HG_NONE, 0u};
     uint32_t kind = HG_HIT_NONE;

@@ -1,5 +1,6 @@
 // hg_devprobe.hip — TEST INFRASTRUCTURE ONLY (make devprobe -> halogen/devprobe/libhg_devprobe.so; never linked into
-// libhalogen_hip.so).  One elementwise entry point that evaluates the device building blocks of hg_device.h,
+// libhalogen_hip.so).  One elementwise entry point that evaluates the device building blocks of hg_device.h
+// (20-23: hg_dev_math.h, hg_dev_sampler.h; 30-33: hg_dev_isect.h; 50-51: hg_dev_sky.h; 52-58: hg_dev_shade.h),
 // hg_fmath.h and hg_pack.h themselves — the functions the megakernels call, not restatements — on caller-supplied
 // inputs, so tests/test_gpu_device_units.py can put each next to its CPU-oracle counterpart (oracle/hg_oracle.c
 // hgo_fmath and the hgo_*_batch exports) bit for bit.

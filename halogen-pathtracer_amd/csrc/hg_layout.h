@@ -94,7 +94,7 @@ struct HgKernelParams {
     int32_t tiles_x, rank, n_ranks, n_local_tiles;
     uint32_t stack_depth;  // LDS traversal stack entries per lane
     uint32_t mesh_lds_word;  // the mesh records' LDS copy starts at this word (hg_wave_lds_plan below)
-    uint32_t descent_t;    // relaxed while-while threshold (hg_device.h isect_meshes), 0 = classic while-while
+    uint32_t descent_t;    // relaxed while-while threshold (hg_dev_trav.h isect_meshes), 0 = classic while-while
     uint32_t stream_deep;  // streaming kernel: the deep-BLAS shading thresholds (HG_STREAM_TMIN_DEEP / _RESHADE_DEEP)
     uint32_t mat_lds_word;  // the material table's LDS copy starts at this word (kMatLds launches; hg_wave_lds_plan)
     uint32_t* __restrict__ spill;  // per-lane traversal stack entries beyond the LDS part (rarely touched)

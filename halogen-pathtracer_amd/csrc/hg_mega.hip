@@ -93,7 +93,7 @@ size_t hg_mega_lds_bytes(uint32_t stack_depth, int block) {
 // the traversal's register budget: bounceTypes[3] + the bounce index in one word (host guarantees maxBounces <=
 // HG_REGEN_MAX_BOUNCES), frame + sample index in another (n_frames, spp < 2^16, host-chunked), the pixel's ndc /
 // accumulator slot recomputed at each regeneration.
-// Per-lane path state parked in LDS (RowVec3 / RowVec4 rows, hg_device.h): the throughput, radiance and sample sum
+// Per-lane path state parked in LDS (RowVec3 / RowVec4 rows, hg_dev_stack.h): the throughput, radiance and sample sum
 // are touched once per bounce, so they stay out of the registers the traversal needs.
 constexpr uint32_t kRegenLdsState = 9;  // words per lane: throughput, radiance, sample sum
 // Streaming kernel: one more word per lane (row 9, unused since the round-2 LDS accumulator was retired: the leaf-share
@@ -112,7 +112,7 @@ __device__ __forceinline__ f3 sample_mean(const HgKernelParams& kp, f3 sum) {
     return mk(sum.x / sppf, sum.y / sppf, sum.z / sppf);
 }
 
-// The wave's copy of the material table (mat_f4, hg_device.h), made once the lanes' rows are initialised: at spp 1 the
+// The wave's copy of the material table (mat_f4, hg_dev_records.h), made once the lanes' rows are initialised: at spp 1 the
 // table may lie in the sample-sum rows (hg_layout.h hg_wave_lds_plan), which no lane writes or reads after that
 // initialisation (sample_mean above and the one_sample branches of the shading loops: the sum of one sample is the
 // sample).  The render server's waves copy once per lifetime: every upload, a partial one included, stops the server
@@ -129,7 +129,7 @@ __device__ __forceinline__ void mat_lds_begin(const HgKernelParams& kp, uint32_t
 template <bool kCounters, bool kMeshLds, bool kMatLds>
 __global__ __launch_bounds__(HG_STREAM_LB, HG_MEGA_WAVES) void hg_trace_regen_kernel(const HgKernelParams kp) {
     const uint32_t lane = threadIdx.x & 63u;
-    if (kMeshLds) {  // the wave's copy of the mesh records (mesh_f4, hg_device.h)
+    if (kMeshLds) {  // the wave's copy of the mesh records (mesh_f4, hg_dev_records.h)
         mesh_lds_fill(kp, lane);
         wave_lds_sync();
     }
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(HG_STREAM_LB, HG_STREAM_WAVES) void hg_trace_stream
     const RowVec3<kRowSum> s_sum{lane};
     const LeafShare ls{kRowLeaf * 64u};
     const uint32_t nm = uint32_t(kp.n_meshes);
-    if (kMeshLds) {  // the wave's copy of the mesh records (mesh_f4, hg_device.h)
+    if (kMeshLds) {  // the wave's copy of the mesh records (mesh_f4, hg_dev_records.h)
         mesh_lds_fill(kp, lane);
         wave_lds_sync();
     }

@@ -40,12 +40,7 @@ __global__ __launch_bounds__(kQueryBlock, HG_QUERY_WAVES) void hg_query_kernel(c
     }
     const MegaStack stk{threadIdx.x, uint32_t(kQueryBlock), kp.spill + i, kp.spill_stride};
     const Ray ray{mk(ro.x, ro.y, ro.z), mk(rd.x, rd.y, rd.z)};
-    Hit h;
-    h.t = ro.w;  // the closest distance is seeded with t_max (+inf: the path tracer's get_ray_intersection)
-    h.orient = 0.0f;
-    h.pos = mk(0, 0, 0);
-    h.n = mk(0, 0, 0);
-    h.mat = 0;
+    Hit h = hit_none(ro.w);  // the closest distance is seeded with t_max (+inf: the path tracer's get_ray_intersection)
     const uint32_t sph = isect_spheres(kp, ray, h.t);
     MeshBest mb{0.0f, 0.0f, HG_NONE, 0u};
     uint32_t kind = HG_HIT_NONE, object = 0u, prim = 0u;
@@ -79,7 +74,8 @@ __global__ __launch_bounds__(kQueryBlock, HG_QUERY_WAVES) void hg_query_kernel(c
 }
 
 // The first camera ray (sample 0) frame `frame` traces for each listed pixel: camera_ray seeded as hg_trace_kernel
-// seeds it (hg_mega.hip), ndc of :1023-1033.
+// seeds it (hg_mega.hip), ndc of :1023-1033.  (Spelled out here and in the guide kernel of hg_denoise.hip, not shared:
+// a helper that reads W, H and Wu through a reference to kp moves those loads to the kernel's entry.)
 __global__ __launch_bounds__(kQueryBlock) void hg_camera_rays_kernel(const HgKernelParams kp, uint32_t frame,
                                                                      const int2* __restrict__ pixels,
                                                                      float4* __restrict__ rays, uint32_t n) {

@@ -101,7 +101,7 @@ int server_stop(hg_ctx* c) {
     return HG_OK;
 }
 
-// The camera part of a launch's parameter block (everything camera_ray reads, hg_device.h) from the uniforms
+// The camera part of a launch's parameter block (everything camera_ray reads, hg_dev_shade.h) from the uniforms
 void set_camera(HgKernelParams& kp, const hg_params& p) {
     for (int r = 0; r < 3; ++r)
         for (int k = 0; k < 4; ++k) kp.cam[r * 4 + k] = p.camLocalToWorld.m[k * 4 + r];
@@ -260,7 +260,7 @@ int server_start(hg_ctx* c, const HgKernelParams& kp_in, int32_t fc) {
         HG_HIP(c, hipStreamSynchronize(c->stream));
     int rc = ensure_uncached(c, S.ring, size_t(ring) * per_frame);
     if (!rc) rc = ensure_uncached(c, S.done, size_t(ring) * 128u);
-    if (!rc) rc = ensure_uncached(c, S.ctl, HG_SV_CTL_BYTES);  // (polled by scalar loads: hg_device.h sv_sload)
+    if (!rc) rc = ensure_uncached(c, S.ctl, HG_SV_CTL_BYTES);  // (polled by scalar loads: hg_dev_wave.h sv_sload)
     if (!rc && spill_bytes) rc = ensure(c, S.spill, spill_bytes);
     if (rc) return rc;
     // The counts and heads are zeroed on the context stream: after the last lifetime's gates and blends, and before

@@ -101,7 +101,7 @@ inline float4 f4(float x, float y, float z, float w) { return make_float4(x, y, 
 inline float bits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 inline float bits(int32_t i) { float f; std::memcpy(&f, &i, 4); return f; }
 
-// Padded world-space boxes of a mesh root's two children (for the exact mesh skip, hg_device.h mesh_live_mask).
+// Padded world-space boxes of a mesh root's two children (for the exact mesh skip, hg_dev_isect.h mesh_live_mask).
 // The local box corners go through the double-precision inverse of the float worldToLocal the kernel uses;
 // the pad (1e-3 of the box size + 1e-4 of the coordinate magnitude + 1e-5) exceeds by orders of magnitude
 // the float rounding of the reference's local-space slab test (~1e-7 relative), so "misses the padded box"
@@ -190,7 +190,7 @@ inline void set_cull_boxes(const HalogenMeshData& m, const BVHEntry* blas, HgDev
     else dm.cull_a_lo = dm.cull_a_hi = dm.cull_b_lo = dm.cull_b_hi = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
-// The child-pair record layout (hg_device.h node_pair): q0 = (A.lo, refA), q1 = (A.hi, refB), q2 = (B.lo, -), q3 = (B.hi, -)
+// The child-pair record layout (hg_dev_records.h node_pair): q0 = (A.lo, refA), q1 = (A.hi, refB), q2 = (B.lo, -), q3 = (B.hi, -)
 inline void put_pair(float4* r, const BVHEntry& A, const BVHEntry& B, uint32_t ra, uint32_t rb) {
     r[0] = f4(A.boundingCornerA.x, A.boundingCornerA.y, A.boundingCornerA.z, bits(ra));
     r[1] = f4(A.boundingCornerB.x, A.boundingCornerB.y, A.boundingCornerB.z, bits(rb));
@@ -238,7 +238,7 @@ inline void copy_bytes(std::vector<uint8_t>& dst, const void* src, size_t n) {
 }
 
 inline int hg_scene_check_limits(const HgSceneIn& in, HgPackError& err) {
-    // the traversal addresses nodes / triangles with 32-bit byte offsets (hg_device.h ld_off)
+    // the traversal addresses nodes / triangles with 32-bit byte offsets (hg_dev_records.h ld_off)
     if (in.n_nodes >= (1 << 26) || in.n_tris >= (1 << 28))
         return hg_pack_fail(err, HG_E_UNSUPPORTED,
                             "scene too large: %d BLAS entries (max 2^26-1), %d triangles (max 2^28-1)", in.n_nodes,

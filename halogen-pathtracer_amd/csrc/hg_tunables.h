@@ -207,7 +207,7 @@
 #define HG_STREAM_LB 64  // regen / stream kernels: __launch_bounds__ max threads = their one-wave workgroup (256: scratch 32 B vs 24-28 B)
 #endif
 #ifndef HG_CHECK_EXEC
-#define HG_CHECK_EXEC 0  // debug builds: leaf_dist checks its all-lanes-active precondition (hg_device.h)
+#define HG_CHECK_EXEC 0  // debug builds: leaf_dist checks its all-lanes-active precondition (hg_dev_isect.h)
 #endif
 #ifndef HG_MEGA_LDS_STACK
 #define HG_MEGA_LDS_STACK 16  // megakernels: traversal stack entries per lane kept in LDS (deeper ones spill)

@@ -1,5 +1,5 @@
 """ctypes loader of the test-only device probe (halogen-pathtracer_amd/csrc/hg_devprobe.hip, `make devprobe`): one
-elementwise kernel over the device building blocks of hg_device.h / hg_fmath.h / hg_pack.h.  A helper module of
+elementwise kernel over the device building blocks of hg_device.h (the hg_dev_*.h headers) / hg_fmath.h / hg_pack.h.  A helper module of
 tests/test_gpu_device_units.py and tests/test_gpu_shading_units.py; the function codes and element layouts are documented
 in hg_devprobe.hip."""
 import ctypes as C

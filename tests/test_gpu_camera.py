@@ -1,4 +1,4 @@
-"""GPU parity for both forms of the camera ray (hg_device.h camera_ray).
+"""GPU parity for both forms of the camera ray (hg_dev_shade.h camera_ray).
 
 With a focal-disc radius of 0 the kernels skip the focal-disc sample and its sincos (HG_PINHOLE_FAST): the aperture
 point is (+-0, +-0, 0) and its zeros cannot reach the ray as long as no camera translation component is 0.  The

@@ -1,6 +1,6 @@
 """leaf_dist's precondition, checked at run time.
 
-The distributed leaf test (hg_device.h leaf_dist) scans leaf sizes with DPP row shifts and exchanges rays with
+The distributed leaf test (hg_dev_isect.h leaf_dist) scans leaf sizes with DPP row shifts and exchanges rays with
 ds_bpermute: it is exact only when every lane of the wave is active.  The product build relies on the streaming
 kernel calling it at the top level of ballot-exit loops.  The HG_CHECK_EXEC=1 build (make check_exec ->
 halogen/check_exec/libhalogen_hip.so) checks EXEC on every call, falls back to the sequential leaf loop when a lane is

@@ -3,7 +3,7 @@
 The kernels copy every mesh's world->local matrix and header into the wave's LDS only while the table fits the
 per-wave LDS budget (hg_mega.hip mesh_lds_bytes: 16 meshes for the streaming kernel, fewer for the regenerating
 one); larger scenes read the records from global memory.  The exact mesh cull keeps a 64-bit live mask, so meshes
-64 and beyond are never culled (hg_device.h mesh_live_mask).  The benchmark scenes have 7-10 meshes, so both paths
+64 and beyond are never culled (hg_dev_isect.h mesh_live_mask).  The benchmark scenes have 7-10 meshes, so both paths
 are exercised here: the Cornell box with a grid of extra cubes (30 and 75 meshes in all), every kernel, against the
 live CPU oracle, bit for bit and with equal work counters."""
 import numpy as np

@@ -1,6 +1,6 @@
 """The shading half of the device building blocks, one at a time, against the CPU oracle's own functions.
 
-tests/test_gpu_device_units.py covers the intersection half of hg_device.h; this file covers what a path does after the
+tests/test_gpu_device_units.py covers the intersection half of hg_device.h (hg_dev_isect.h, hg_dev_trav.h); this file covers what a path does after the
 hit, with the same probe library (csrc/hg_devprobe.hip fn 50-58, tests/devprobe.py) and the same criterion: sample_sky
 with cube_adjacent, sky_level, lambert, reflect, schlick_adjusted, refract_tir, medium_push / medium_pop (the device's
 eight bytes of a uint64_t against the oracle's array of structs), evaluate_hit with material_brdf, and

@@ -379,7 +379,7 @@ def test_anchors(driver):
 def test_deepest_stack_spill_columns(driver):
     """stack_depth 64, the deepest tree hg_pack_geometry accepts (tests/tree_cases.py chain62 at 40 x 24: 15 tiles, and
     the 1080p image).  What the traversal needs, not the plan's formula again: thread j of a launch pushes stack entry
-    d >= kLds to word (d - kLds) * spill_stride + j of the spill buffer (hg_device.h Stack / RowStack; j = blockIdx *
+    d >= kLds to word (d - kLds) * spill_stride + j of the spill buffer (hg_dev_stack.h Stack / RowStack; j = blockIdx *
     blockDim + threadIdx, hg_mega.hip), with kLds = 16 in the lockstep and regenerating kernels and 12 in the streaming
     one and the server.  So the buffer must hold word (63 - kLds) * stride + threads - 1, and a column base j must stay
     below the stride."""

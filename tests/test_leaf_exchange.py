@@ -1,4 +1,4 @@
-"""The distributed leaf test of the streaming kernel (hg_device.h leaf_dist) restated in numpy and
+"""The distributed leaf test of the streaming kernel (hg_dev_isect.h leaf_dist) restated in numpy and
 checked against the reference's sequential leaf loop (HalgoenCompute.compute:404-420, the order the oracle
 follows).
 
