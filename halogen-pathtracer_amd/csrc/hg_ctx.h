@@ -33,6 +33,9 @@ struct hg_ctx {
     // identical re-upload (the reference re-uploads on every camera move) is detected and skipped
     std::vector<uint8_t> scene_copy[5];
     std::vector<HgDevMesh> dev_meshes;  // the device mesh table of the last upload (partial re-uploads start from it)
+    // the cull table of dev_meshes (hg_cull.h) as it lies in `cull`, uploaded wherever the mesh table is
+    DevBuf cull;
+    HgCullTable cull_table;
     uint64_t scene_uploads = 0, scene_uploads_skipped = 0, scene_uploads_partial = 0, scene_uploads_vouched = 0;
     uint64_t geometry_gen = 0;  // hg_upload_scene_gen: the caller's geometry generation of the last upload (0: none)
     // Mesh updates (hg_refit_mesh, hg_rebuild_mesh[_sah], hg_deform_mesh, hg_skin_mesh: one path, update_mesh of

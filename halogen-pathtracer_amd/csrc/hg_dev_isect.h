@@ -26,37 +26,49 @@ __device__ __forceinline__ void pair_dist(const NodePair& r, f3 o, f3 inv, float
     dB = ray_aabb(xyz(r.q2), xyz(r.q3), o, inv);
 }
 
+// One sphere of isect_spheres: record (cr, am, b) of sphere i against the ray; updates the closest accepted sphere
+__device__ __forceinline__ void isect_sphere(const HgKernelParams& kp, const Ray& ray, f3 inv, uint32_t i, float4 cr,
+                                             float4 am, float4 b, float& closest, uint32_t& best) {
+    if (!(ray_aabb(xyz(am), xyz(b), ray.o, inv) < kp.far_)) return;
+    // sphere_intersection :266-303
+    f3 center = xyz(cr);
+    f3 sh = ray.o - center;
+    float bq = 2.0f * dot(sh, ray.d);
+    float cq = dot(sh, sh) - cr.w * cr.w;
+    float disc = bq * bq - 4.0f * cq;
+    if (!(disc >= 0.0f)) return;  // rayT = INF: never accepted
+    float hd = (-bq - __builtin_sqrtf(disc)) / 2.0f;
+    uint32_t back = 0;
+    if (hd < 0.0f) {
+        hd = (-bq + __builtin_sqrtf(disc)) / 2.0f;
+        back = 0x80000000u;
+    }
+    if (hd < closest && hd > 0.0001f) {
+        closest = hd;
+        best = i | back;
+    }
+}
+
 // Returns the closest accepted sphere as index | (orientation < 0) << 31 (HG_NONE if none), its distance in t;
 // position/normal/material are resolved after the mesh pass (resolve_sphere), with the same arithmetic.
-__device__ uint32_t isect_spheres(const HgKernelParams& kp, const Ray& ray, float& t) {  // :357-376
+// inv: 1 / ray.d by rcp_exact, which the mesh cull of the same ray start uses too.  The records of two spheres are
+// fetched before the first is tested (one wait on the scalar cache per pair); they are tested in buffer order.
+__device__ uint32_t isect_spheres(const HgKernelParams& kp, const Ray& ray, float& t, f3 inv) {  // :357-376
     float closest = t;
     uint32_t best = HG_NONE;
-    f3 inv = mk(rcp_exact(ray.d.x), rcp_exact(ray.d.y), rcp_exact(ray.d.z));
-    for (int i = 0; i < kp.n_spheres; ++i) {
-        const float4 cr = ldc(kp.spheres, 3 * i);
-        const float4 am = ldc(kp.spheres, 3 * i + 1);
-        const float4 b = ldc(kp.spheres, 3 * i + 2);
-        if (!(ray_aabb(xyz(am), xyz(b), ray.o, inv) < kp.far_)) continue;
-        // sphere_intersection :266-303
-        f3 center = xyz(cr);
-        f3 sh = ray.o - center;
-        float bq = 2.0f * dot(sh, ray.d);
-        float cq = dot(sh, sh) - cr.w * cr.w;
-        float disc = bq * bq - 4.0f * cq;
-        if (!(disc >= 0.0f)) continue;  // rayT = INF: never accepted
-        float hd = (-bq - __builtin_sqrtf(disc)) / 2.0f;
-        uint32_t back = 0;
-        if (hd < 0.0f) {
-            hd = (-bq + __builtin_sqrtf(disc)) / 2.0f;
-            back = 0x80000000u;
-        }
-        if (hd < closest && hd > 0.0001f) {
-            closest = hd;
-            best = uint32_t(i) | back;
-        }
+    const uint32_t n = uint32_t(kp.n_spheres);
+    for (uint32_t i = 0; i < n; i += 2u) {
+        const uint32_t j = i + 1u < n ? i + 1u : i;  // (an odd count's last pair: the same record twice, tested once)
+        const float4 cr0 = ldc(kp.spheres, 3 * i), am0 = ldc(kp.spheres, 3 * i + 1), b0 = ldc(kp.spheres, 3 * i + 2);
+        const float4 cr1 = ldc(kp.spheres, 3 * j), am1 = ldc(kp.spheres, 3 * j + 1), b1 = ldc(kp.spheres, 3 * j + 2);
+        isect_sphere(kp, ray, inv, i, cr0, am0, b0, closest, best);
+        if (j != i) isect_sphere(kp, ray, inv, j, cr1, am1, b1, closest, best);
     }
     t = closest;
     return best;
+}
+__device__ __forceinline__ uint32_t isect_spheres(const HgKernelParams& kp, const Ray& ray, float& t) {
+    return isect_spheres(kp, ray, t, mk(rcp_exact(ray.d.x), rcp_exact(ray.d.y), rcp_exact(ray.d.z)));
 }
 __device__ __forceinline__ void resolve_sphere(const HgKernelParams& kp, const Ray& ray, uint32_t ref, Hit& h) {
     const uint32_t i = ref & 0x7FFFFFFFu;
@@ -68,29 +80,36 @@ __device__ __forceinline__ void resolve_sphere(const HgKernelParams& kp, const R
     h.mat = __float_as_uint(kp.spheres[3 * i + 1].w);
 }
 
-// Exact mesh skip (HgDevMesh::cull_*): bit m of the result is clear when the ray certainly misses both children of
-// mesh m's root in the reference's local-space test, or meets them only beyond `best_t` — the reference would test
-// those two boxes, push nothing and find nothing there.  Meshes >= 64 are never culled.
+// Exact mesh skip over the cull table (hg_cull.h; the boxes are HgDevMesh::cull_*): bit m of the result is clear when
+// the ray certainly misses both children of mesh m's root in the reference's local-space test, or meets them only
+// beyond `best_t` — the reference would test those two boxes, push nothing and find nothing there.  A mesh has one
+// entry (its children tile their union: the union box) or two (HG_CULL_MORE on the first), and its bit is cleared only
+// when every one is far.  Meshes without an entry (not cullable, or >= 64) are never culled.  Two entries, tags
+// included, come with one 64-B scalar fetch.
+__device__ __forceinline__ void cull_entry(float4 lo, float4 hi, f3 wo, f3 winv, float lim, bool& far, uint64_t& live,
+                                           uint32_t& culled) {
+    const float d = ray_aabb(xyz(lo), xyz(hi), wo, winv);
+    far = far && (d == HG_INF || d > lim);  // NaN never skips
+    const uint32_t tag = __float_as_uint(lo.w);
+    if (!(tag & HG_CULL_MORE)) {  // the mesh's last entry
+        if (far) {
+            live &= ~(1ull << (tag & HG_CULL_MESH_MASK));
+            culled++;
+        }
+        far = true;
+    }
+}
 __device__ __forceinline__ uint64_t mesh_live_mask(const HgKernelParams& kp, f3 wo, f3 winv, float best_t,
                                                    uint32_t& culled) {
     uint64_t live = ~0ull;
     const float lim = best_t * 1.0001f + 1e-4f;
-    const int ncull = kp.n_meshes < 64 ? kp.n_meshes : 64;
-    static_assert(sizeof(HgDevMesh) % 16 == 0 && offsetof(HgDevMesh, cull_a_lo) % 16 == 0, "float4 records");
-    const float4* mrec = reinterpret_cast<const float4*>(kp.meshes);
-    constexpr uint32_t kRec = sizeof(HgDevMesh) / 16, kCull = offsetof(HgDevMesh, cull_a_lo) / 16;
-    for (int m = 0; m < ncull; ++m) {
-        const float4 hdr = ldc(mrec, m * kRec + kCull - 1);  // root_ref, tri_offset, material, cullable
-        if (!__float_as_uint(hdr.w)) continue;
-        const float4 alo = ldc(mrec, m * kRec + kCull), ahi = ldc(mrec, m * kRec + kCull + 1),
-                     blo = ldc(mrec, m * kRec + kCull + 2), bhi = ldc(mrec, m * kRec + kCull + 3);
-        const float dA = ray_aabb(xyz(alo), xyz(ahi), wo, winv);
-        const float dB = ray_aabb(xyz(blo), xyz(bhi), wo, winv);
-        const bool farA = dA == HG_INF || dA > lim, farB = dB == HG_INF || dB > lim;  // NaN never skips
-        if (farA && farB) {
-            live &= ~(1ull << m);
-            culled++;
-        }
+    const uint32_t n = kp.n_cull;
+    bool far = true;  // every entry of the current mesh so far is far
+    for (uint32_t i = 0; i < n; i += 2u) {  // (the table is allocated to an even number of entries)
+        const float4 lo0 = ldc(kp.cull, 2 * i), hi0 = ldc(kp.cull, 2 * i + 1), lo1 = ldc(kp.cull, 2 * i + 2),
+                     hi1 = ldc(kp.cull, 2 * i + 3);
+        cull_entry(lo0, hi0, wo, winv, lim, far, live, culled);
+        if (i + 1u < n) cull_entry(lo1, hi1, wo, winv, lim, far, live, culled);
     }
     return live;
 }

@@ -130,7 +130,7 @@ template <bool kMeshLds = false, class Stk>
 __device__ __forceinline__ Hit intersect(const HgKernelParams& kp, const Ray& ray, Counters& c, const Stk& stk) {  // get_ray_intersection :474-485
     Hit h = hit_none(HG_INF);
     c.rays++;
-    const uint32_t sph = isect_spheres(kp, ray, h.t);
+    const uint32_t sph = isect_spheres(kp, ray, h.t);  // (its 1 / d and isect_meshes' are one computation once inlined)
     if (!isect_meshes<kMeshLds>(kp, ray, h, c, stk) && sph != HG_NONE) resolve_sphere(kp, ray, sph, h);
     return h;
 }
@@ -152,14 +152,14 @@ template <bool kMeshLds = false>
 __device__ __forceinline__ void trav_begin(const HgKernelParams& kp, const Ray& ray, Trav& t, Counters& c) {
     c.rays++;
     t.sph_t = HG_INF;
-    t.sph = isect_spheres(kp, ray, t.sph_t);
+    const f3 winv = mk(rcp_exact(ray.d.x), rcp_exact(ray.d.y), rcp_exact(ray.d.z));  // once for spheres and cull
+    t.sph = isect_spheres(kp, ray, t.sph_t, winv);
     t.best_t = t.sph_t;  // closestIntersection.rayT starts at the sphere hit (:381)
     t.best_u = 0.0f;
     t.best_v = 0.0f;
     t.best_tri = HG_NONE;
     t.best_mesh = 0;
     uint32_t culled = 0;
-    const f3 winv = mk(rcp_exact(ray.d.x), rcp_exact(ray.d.y), rcp_exact(ray.d.z));
     t.live = mesh_live_mask(kp, ray.o, winv, t.best_t, culled);
     c.aabb += 2 * culled;
     t.sp = 0;

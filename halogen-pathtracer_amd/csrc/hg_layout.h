@@ -21,6 +21,8 @@
 //   normals        48 B per triangle (n0, n1 - n0, n2 - n0), read once per accepted hit.
 //   meshes         144 B per mesh (HgDevMesh): full worldToLocal (16 floats, Unity column-major), root ref,
 //                  triangle offset, material index, the exact-cull boxes.
+//   cull table     32 B per entry, one or two entries per cullable mesh below 64 (hg_cull.h): the exact-cull boxes
+//                  again, contiguous, which is all a ray start reads of the meshes.
 //   spheres        48 B: (centre, radius), (cornerA, material bits), (cornerB, 0).
 //   materials      80 B: albedo; (specular.rgb, metallic); (emissive.rgb*intensity, roughness);
 //                  (absorption.xyz, ior); (priority, medium id, roughness^2, 0).
@@ -47,6 +49,12 @@ struct alignas(16) HgDevMesh {
     // boxes, push nothing and find nothing — so the mesh is skipped and only its 2 AABB tests are counted.
     float4 cull_a_lo, cull_a_hi, cull_b_lo, cull_b_hi;
 };
+
+// The cull table (hg_cull.h): what a ray start reads of the boxes above, 32 B per entry: (lo.xyz, tag), (hi.xyz, 0).
+// tag: the mesh index, and HG_CULL_MORE when the next entry belongs to the same mesh.
+#define HG_CULL_MAX_MESHES 64u
+#define HG_CULL_MESH_MASK 0x3Fu
+#define HG_CULL_MORE 0x80000000u
 
 // Everything the trace kernel needs, passed by value as the kernel argument.
 struct HgKernelParams {
@@ -104,8 +112,10 @@ struct HgKernelParams {
     uint32_t cube_mip_offset[HG_MAX_CUBE_MIPS];  // in float4 texels
     // scene
     int32_t n_materials;  // records of `materials` (what a wave copies into its LDS)
+    uint32_t n_cull;      // entries of `cull` that belong to meshes below n_meshes
     const float4* __restrict__ spheres;
     const HgDevMesh* __restrict__ meshes;
+    const float4* __restrict__ cull;  // the cull table, 2 float4 per entry, an even number of entries allocated
     const float4* __restrict__ materials;
     const float4* __restrict__ nodes;
     const uint2* __restrict__ leaves;

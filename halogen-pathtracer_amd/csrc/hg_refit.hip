@@ -186,7 +186,9 @@ int refit_device(hg_ctx* c, const HgRefitPlan& plan, DevBuf& list, const std::ve
         c->root_pairs[size_t(j)] = pair;
         set_cull_boxes_kept(meshes[j], pair, c->dev_meshes[size_t(j)]);
     }
+    hg_cull_table(c->dev_meshes.data(), c->dev_meshes.size(), c->cull_table);
     if (int rc = upload(c, c->meshes, c->dev_meshes.data(), c->dev_meshes.size() * sizeof(HgDevMesh))) return rc;
+    if (int rc = upload(c, c->cull, c->cull_table.q.data(), c->cull_table.q.size() * sizeof(float4))) return rc;
     HG_HIP(c, hipStreamSynchronize(c->stream));
     c->geometry_stale = true;
     c->geometry_gen = geometry_generation;

@@ -127,6 +127,8 @@ void set_scene(HgKernelParams& kp, const hg_ctx* c, uint32_t descent_t) {
     kp.descent_t = descent_t;
     kp.spheres = static_cast<const float4*>(c->spheres.p);
     kp.meshes = static_cast<const HgDevMesh*>(c->meshes.p);
+    kp.cull = static_cast<const float4*>(c->cull.p);
+    kp.n_cull = hg_cull_count(c->cull_table, kp.n_meshes);  // (the caller has set kp.n_meshes)
     kp.materials = static_cast<const float4*>(c->materials.p);
     kp.n_materials = c->n_materials;
     kp.nodes = static_cast<const float4*>(c->nodes.p);

@@ -252,7 +252,7 @@ void hg_destroy(hg_ctx* c) {
     sv_trace("destroy: context stream idle");
     for (hg_ctx::TraceLane& L : c->lanes)
         if (L.stream) (void)hipStreamSynchronize(L.stream);
-    for (DevBuf* b : {&c->spheres, &c->meshes, &c->materials, &c->nodes, &c->leaves, &c->tris, &c->normals, &c->cube,
+    for (DevBuf* b : {&c->spheres, &c->meshes, &c->cull, &c->materials, &c->nodes, &c->leaves, &c->tris, &c->normals, &c->cube,
                       &c->acc, &c->counters_dev, &c->spill, &c->lost, &c->query_in, &c->query_out, &c->guide0,
                       &c->guide1, &c->denoise_work[0], &c->denoise_work[1], &c->refit_in, &c->refit_raw, &c->lbvh.points,
                       &c->lbvh.partial, &c->lbvh.bounds, &c->lbvh.codes, &c->lbvh.index, &c->lbvh.codes_sorted,
@@ -321,6 +321,8 @@ int commit_scene(hg_ctx* c, const HgSceneIn& in, HgScenePack& pack, HgUploadDeci
     for (int k = 0; k < (partial ? 3 : 5); ++k) copy_bytes(c->scene_copy[k], in.src(k), in.bytes(k));
     HG_HIP(c, hipStreamSynchronize(c->stream));  // host staging vectors die at return
     c->dev_meshes.swap(pack.dm);
+    c->cull_table.q.swap(pack.cull.q);
+    c->cull_table.n = pack.cull.n;
     c->scene_uploads++;
     if (partial) {
         c->scene_uploads_partial++;
@@ -395,6 +397,7 @@ int hg_upload_scene_gen(hg_ctx* c, uint64_t geometry_generation, const HalogenSp
     if ((rc = upload(c, c->spheres, pack.sph.data(), pack.sph.size() * sizeof(float4)))) return rc;
     if ((rc = upload(c, c->materials, pack.mat.data(), pack.mat.size() * sizeof(float4)))) return rc;
     if ((rc = upload(c, c->meshes, pack.dm.data(), pack.dm.size() * sizeof(HgDevMesh)))) return rc;
+    if ((rc = upload(c, c->cull, pack.cull.q.data(), pack.cull.q.size() * sizeof(float4)))) return rc;
     if (!partial) {
         if ((rc = upload(c, c->nodes, pack.rec.data(), pack.rec.size() * sizeof(float4)))) return rc;
         if ((rc = upload(c, c->leaves, pack.leaf.data(), pack.leaf.size() * sizeof(uint2)))) return rc;

@@ -36,6 +36,7 @@ static_assert(sizeof(uint2) == HG_UINT2_BYTES && alignof(uint2) == HG_UINT2_BYTE
 
 #include "hg_host_pool.h"
 #include "hg_layout.h"
+#include "hg_cull.h"
 #include "hg_refit.h"
 #include "hg_refit_plan.h"
 
@@ -86,10 +87,11 @@ struct HgSceneIn {
     }
 };
 
-// The host staging of the device scene (hg_layout.h).  A partial pack fills sph, mat and dm only.
+// The host staging of the device scene (hg_layout.h).  A partial pack fills sph, mat, dm and cull only.
 struct HgScenePack {
     std::vector<float4> sph, mat;
     std::vector<HgDevMesh> dm;
+    HgCullTable cull;  // of dm (hg_cull.h): every function that fills dm ends by deriving it
     std::vector<float4> rec;
     std::vector<uint2> leaf;
     std::vector<float> t9;  // (v0, e1, e2) of tri_load, packed per triangle
@@ -355,6 +357,7 @@ inline int hg_pack_mesh_table(const HgSceneIn& in, const std::vector<HgDevMesh>&
         if (int rc = check_mesh_material(in, mi, err)) return rc;
         fill_mesh_record(in.meshes[mi], in.blas, dm[mi]);
     }
+    hg_cull_table(dm.data(), dm.size(), out.cull);
     return HG_OK;
 }
 
@@ -401,6 +404,7 @@ inline int hg_pack_mesh_table_kept(const HgSceneIn& in, const std::vector<HgDevM
         dm[size_t(mi)].material = m.materialIndex;
         set_cull_boxes_kept(m, kept[size_t(mi)], dm[size_t(mi)]);
     }
+    hg_cull_table(dm.data(), dm.size(), out.cull);
     return HG_OK;
 }
 
@@ -552,6 +556,7 @@ inline int hg_pack_geometry(const HgSceneIn& in, HgScenePack& out, HgPackError& 
         return hg_pack_fail(err, HG_E_UNSUPPORTED, "BLAS too large: %zu device node records", rec.size() / 4);
     if (rec.empty()) new_record();
     if (leaf.empty()) leaf.push_back(make_uint2(0, 0));
+    hg_cull_table(dm.data(), dm.size(), out.cull);
     out.stack_depth = hg_stack_depth(max_depth);
     return HG_OK;
 }
