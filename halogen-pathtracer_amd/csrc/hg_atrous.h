@@ -1,8 +1,8 @@
 // hg_atrous.h — the display denoiser of hg_readback_begin_denoised (include/halogen_abi.h), one definition for the
-// device kernels (hg_denoise.hip) and the host twin hg_denoise_host (hg_host.cpp): an edge-avoiding a-trous filter
-// (Dammertz, Sewtz, Hanika, Lensch: "Edge-Avoiding A-Trous Wavelet Transform for fast Global Illumination Filtering",
-// HPG 2010) over the colour, the first-hit normal and the first-hit distance along the ray (in place of the paper's
-// position).  Not in the reference.
+// device kernels (hg_denoise.hip) and the host twin hg_denoise_host (hg_host_denoise.cpp): an edge-avoiding a-trous
+// filter (Dammertz, Sewtz, Hanika, Lensch: "Edge-Avoiding A-Trous Wavelet Transform for fast Global Illumination
+// Filtering", HPG 2010) over the colour, the first-hit normal and the first-hit distance along the ray (in place of
+// the paper's position).  Not in the reference.
 //
 // The contract, in the order the arithmetic is done (fp32, no contraction: both sides build with -ffp-contract=off):
 //   input       colour C (rgba), guide0 = (normal.xyz, t), guide1 = (albedo.rgb, kind); a miss has t = +inf

@@ -1,10 +1,10 @@
-// hg_deform.hip — deforming geometry from where its users hold it, the vertices: hg_set_mesh_vertices binds a mesh's index
-// list to its tree on the device, hg_deform_mesh / hg_deform_mesh_device pack the 72-byte triangles from vertex arrays
-// there, hg_set_mesh_skin / hg_skin_mesh / hg_skin_mesh_device produce those vertices by linear-blend skinning (the
-// contract: hg_skin.h; the host twin: hg_skin_vertices, hg_host.cpp).  The deform and skin entry points fill a MeshUpdate
-// whose source is vertices or a palette; update_mesh (hg_refit.hip) takes from here the checks of that source
-// (vertex_source_check, before the tree's checks and before anything is launched) and the source as packed triangles
-// (vertex_source_device, after the quiesce), and goes on as for any other triangles.  Not in the reference.
+// hg_deform.hip — deforming geometry from where its users hold it, the vertices: hg_set_mesh_vertices binds a mesh's
+// index list to its tree on the device, hg_deform_mesh / hg_deform_mesh_device pack the 72-byte triangles from vertex
+// arrays there, hg_set_mesh_skin / hg_skin_mesh / hg_skin_mesh_device produce those vertices by linear-blend skinning
+// (the contract: hg_skin.h; the host twin: hg_skin_vertices, hg_host_mesh.cpp).  The deform and skin entry points fill
+// a MeshUpdate whose source is vertices or a palette; update_mesh (hg_refit.hip) takes from here the checks of that
+// source (vertex_source_check, before the tree's checks and before anything is launched) and the source as packed
+// triangles (vertex_source_device, after the quiesce), and goes on as for any other triangles.  Not in the reference.
 //
 // With HG_DEFORM_NORMALS the vertex normals are recomputed from the moved faces between the vertex source and the pack
 // (the contract: hg_normals.h; the host twin: hg_vertex_normals), through the adjacency hg_set_mesh_vertices_opt bound.

@@ -1,5 +1,5 @@
 // hg_lbvh.h — the topology of a rebuilt BLAS (hg_build_blas_lbvh, hg_rebuild_mesh, hg_rebuild_mesh_device;
-// include/halogen_abi.h), one definition for the device kernels (hg_lbvh.hip) and the host twin (hg_host.cpp).  A
+// include/halogen_abi.h), one definition for the device kernels (hg_lbvh.hip) and the host twin (hg_host_lbvh.cpp).  A
 // rebuild gives one mesh a new tree over its moved triangles: a linear BVH, that is the triangles in Morton order, cut
 // into leaves of L, under Karras' radix tree (Karras 2012, "Maximizing Parallelism in the Construction of BVHs,
 // Octrees, and k-d Trees").  Every choice is made here, so that both sides build the same tree from the same floats.

@@ -1,8 +1,8 @@
 // hg_lbvh.hip — hg_rebuild_mesh / hg_rebuild_mesh_device: a new tree for one mesh of the device scene, built on the
 // device over the mesh's own triangle and record storage (the contract: hg_lbvh.h; the host twin: hg_build_blas_lbvh,
-// hg_host.cpp).  Not in the reference.  Here: the kernels, the two builds (build_lbvh_device, build_sah_device: step 5
-// of update_mesh, hg_refit.hip, which checks before them and adopts the tree after them) and the four entry points,
-// which fill a MeshUpdate.
+// hg_host_lbvh.cpp).  Not in the reference.  Here: the kernels, the two builds (build_lbvh_device, build_sah_device:
+// step 5 of update_mesh, hg_refit.hip, which checks before them and adopts the tree after them) and the four entry
+// points, which fill a MeshUpdate.
 //
 // The build, all on the context stream and ordered by it alone (no float atomics, no kernel that waits on another
 // workgroup): key points and per-workgroup bounds, the final bounds in one small workgroup, the Morton codes, rocprim's

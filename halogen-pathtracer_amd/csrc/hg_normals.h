@@ -1,6 +1,6 @@
 // hg_normals.h — area-weighted vertex normals of a mesh from its positions and its index list (hg_vertex_normals,
 // HG_DEFORM_NORMALS; include/halogen_abi.h), one definition for the two device kernels (hg_deform.hip) and the host
-// twin (hg_host.cpp), and the host-side builder of the inverted index both sum through.  No HIP in it.  Not in the
+// twin (hg_host_mesh.cpp), and the host-side builder of the inverted index both sum through.  No HIP in it.  Not in the
 // reference.
 //
 // The contract, in the order the arithmetic is done (fp32, no contraction: both sides build with -ffp-contract=off):

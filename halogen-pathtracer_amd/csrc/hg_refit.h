@@ -1,7 +1,7 @@
 // hg_refit.h — the boxes of a refitted BLAS (hg_refit_blas, hg_refit_mesh, hg_refit_mesh_device; include/halogen_abi.h),
-// one definition for the device kernels (hg_refit.hip) and the host twin (hg_host.cpp).  A refit keeps a tree's
+// one definition for the device kernels (hg_refit.hip) and the host twin (hg_host_mesh.cpp).  A refit keeps a tree's
 // topology and recomputes every box from the (moved) triangles, so that the result is what BVHGenerator's arithmetic
-// (hg_host.cpp: TriangleRangeBounds, UnityBounds) gives for the same triangle sets.  Not in the reference.
+// (hg_host_bounds.h: a folded range's UnityBounds, padded) gives for the same triangle sets.  Not in the reference.
 //
 // The contract, in the order the arithmetic is done (fp32, no contraction: both sides build with -ffp-contract=off):
 //   raw box     of a triangle set: per component hg_fminf / hg_fmaxf over the nine coordinates pointA/B/C of each

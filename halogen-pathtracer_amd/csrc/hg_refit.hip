@@ -3,9 +3,9 @@
 // hg_scene_readback hands out the device scene's arrays for tests.  Not in the reference.
 //
 // An update replaces one mesh's triangles and recomputes every box of its tree on the device (the contract: hg_refit.h;
-// the host twin: hg_refit_blas, hg_host.cpp), over the old topology (a refit) or a new one (hg_lbvh.hip), from 72-byte
-// triangles or from vertices or a bone palette (hg_deform.hip).  The ten entry points fill a MeshUpdate (hg_rt.h);
-// update_mesh runs, once and in this order:
+// the host twin: hg_refit_blas, hg_host_mesh.cpp), over the old topology (a refit) or a new one (hg_lbvh.hip), from
+// 72-byte triangles or from vertices or a bone palette (hg_deform.hip).  The ten entry points fill a MeshUpdate
+// (hg_rt.h); update_mesh runs, once and in this order:
 //   1  null context, hg_ctx_flush;
 //   2  every refusal that needs no device, with nothing launched or allocated before the last of them: the vertex
 //      binding and skin (hg_deform.hip), the tree (hg_mesh_trees.h, which has no HIP in it and is tested on the CPU),

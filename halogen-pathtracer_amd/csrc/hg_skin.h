@@ -1,6 +1,6 @@
 // hg_skin.h — linear-blend skinning of one vertex (hg_skin_vertices, hg_skin_mesh, hg_skin_mesh_device;
 // include/halogen_abi.h) and the host-side checks of a vertex binding, one definition for the device kernel
-// (hg_deform.hip) and the host twin (hg_host.cpp).  Not in the reference.
+// (hg_deform.hip) and the host twin (hg_host_mesh.cpp).  Not in the reference.
 //
 // The contract, in the order the arithmetic is done (fp32, no contraction: both sides build with -ffp-contract=off):
 //   bone        12 floats, a row-major 3 x 4 matrix: rows of (x y z t).

@@ -1,6 +1,6 @@
 // asan_denoise — AddressSanitizer + UndefinedBehaviorSanitizer driver of the host denoiser (hg_denoise_host,
-// csrc/hg_host.cpp with the filter of csrc/hg_atrous.h), built with g++ -fsanitize=address,undefined straight from
-// hg_host.cpp (make -C halogen-pathtracer_amd asan_denoise; tests/test_denoise.py).
+// csrc/hg_host_denoise.cpp with the filter of csrc/hg_atrous.h), built with g++ -fsanitize=address,undefined with the
+// host sources (make -C halogen-pathtracer_amd asan_denoise; tests/test_denoise.py).
 //
 //   asan_denoise SEED
 // filters random 1x1, 1x7, 7x1 and 37x23 images (exactly sized buffers, so a tap outside the image is a heap overflow),

@@ -1,5 +1,5 @@
-// asan_lbvh.cpp — hg_build_blas_lbvh (hg_host.cpp over csrc/hg_lbvh.h), the host twin of the device rebuild, under
-// AddressSanitizer + UBSan (make asan_lbvh; tests/test_lbvh.py), on the input classes of the CPU tests: random meshes of
+// asan_lbvh.cpp — hg_build_blas_lbvh (hg_host_lbvh.cpp over csrc/hg_lbvh.h), the host twin of the device rebuild,
+// under AddressSanitizer + UBSan (make asan_lbvh; tests/test_lbvh.py), on the input classes of the CPU tests: meshes of
 // every small count, identical triangles, meshes flat on one, two and three axes, tiny, huge and denormal extents, sums
 // that overflow, key points one ulp apart, a key point at pmax, NaN coordinates.  Whatever the input: a code or a tree
 // that is a partition of the triangles, no deeper than the bound, which hg_refit_blas leaves as it is; nothing outside
@@ -11,17 +11,7 @@
 #include <random>
 #include <vector>
 
-#include "halogen_abi.h"
-#include "hg_lbvh.h"
-
-static int failures = 0;
-#define EXPECT(c)                                                      \
-    do {                                                               \
-        if (!(c)) {                                                    \
-            std::printf("FAILED %s:%d %s\n", __FILE__, __LINE__, #c); \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
+#include "lbvh_check.h"
 
 static void run(const std::vector<HalogenTriangle>& tris, int32_t L) {
     const int32_t n = int32_t(tris.size());
@@ -35,53 +25,8 @@ static void run(const std::vector<HalogenTriangle>& tris, int32_t L) {
     const int64_t rc = hg_build_blas_lbvh(tris.data(), n, L, order.data(), out.data(), nodes.data(), int64_t(nodes.size()));
     EXPECT(rc == int64_t(nodes.size()));
     if (rc < 0) return;
-    std::vector<int> seen(size_t(n), 0);
-    for (int32_t k = 0; k < n; ++k) {
-        EXPECT(order[size_t(k)] >= 0 && order[size_t(k)] < n);
-        if (order[size_t(k)] < 0 || order[size_t(k)] >= n) return;
-        seen[size_t(order[size_t(k)])]++;
-        EXPECT(!std::memcmp(&out[size_t(k)], &tris[size_t(order[size_t(k)])], sizeof(HalogenTriangle)));
-    }
-    for (int s : seen) EXPECT(s == 1);
-    // the walk: every entry once, leaves a partition in steps of L, depth inside the bound
-    std::vector<int> covered(size_t(n), 0);
-    std::vector<std::pair<uint32_t, uint32_t>> stack{{0u, 0u}};
-    size_t reached = 0;
-    uint32_t deepest = 0;
-    while (!stack.empty() && reached <= nodes.size()) {
-        const auto [g, d] = stack.back();
-        stack.pop_back();
-        ++reached;
-        deepest = std::max(deepest, d);
-        EXPECT(g < nodes.size());
-        if (g >= nodes.size()) return;
-        const BVHEntry& e = nodes[g];
-        if (e.triangleCount) {
-            EXPECT(e.indexA % uint32_t(L) == 0 && e.triangleCount <= uint32_t(L) &&
-                   uint64_t(e.indexA) + e.triangleCount <= uint64_t(n));
-            for (uint32_t t = e.indexA; t < e.indexA + e.triangleCount && t < uint32_t(n); ++t) covered[t]++;
-        } else {
-            stack.push_back({e.indexA + 1, d + 1});
-            stack.push_back({e.indexA, d + 1});
-        }
-    }
-    EXPECT(reached == nodes.size());
-    for (int s : covered) EXPECT(s == 1);
-    EXPECT(deepest <= hg_lbvh_depth_bound(K) && deepest <= HG_LBVH_MAX_DEPTH);
-    std::vector<BVHEntry> again = nodes;
-    EXPECT(hg_refit_blas(out.data(), n, again.data(), int32_t(again.size())) == HG_OK);
-    EXPECT(!std::memcmp(again.data(), nodes.data(), nodes.size() * sizeof(BVHEntry)));
-}
-
-static std::vector<HalogenTriangle> make(std::mt19937& rng, int n, float lo, float hi, int flat_mask) {
-    std::uniform_real_distribution<float> pos(lo, hi);
-    std::vector<HalogenTriangle> t(static_cast<size_t>(n));
-    for (HalogenTriangle& h : t) {
-        float* p = &h.pointA.x;  // pointA, pointB, pointC: nine floats
-        for (int k = 0; k < 9; ++k) p[k] = (flat_mask >> (k % 3)) & 1 ? 0.25f : pos(rng);
-        h.normalA = h.normalB = h.normalC = {0.0f, 1.0f, 0.0f};
-    }
-    return t;
+    if (!check_order(tris, order, out)) return;
+    check_tree(nodes, out, uint32_t(L), uint32_t(L), K);  // leaves a partition in steps of L
 }
 
 int main() {

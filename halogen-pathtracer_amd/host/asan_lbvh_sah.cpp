@@ -1,6 +1,6 @@
-// asan_lbvh_sah.cpp — hg_build_blas_lbvh_sah (hg_host.cpp over the second contract of csrc/hg_lbvh.h), the host twin of the
-// device rebuild with leaves chosen by surface area, under AddressSanitizer + UBSan (make asan_lbvh_sah; tests/
-// test_lbvh_sah.py), on the input classes of the CPU tests: random meshes of every count around the largest leaf and
+// asan_lbvh_sah.cpp — hg_build_blas_lbvh_sah (hg_host_lbvh.cpp over the second contract of csrc/hg_lbvh.h), the host
+// twin of the device rebuild with leaves chosen by surface area, under AddressSanitizer + UBSan (make asan_lbvh_sah;
+// tests/test_lbvh_sah.py), on the input classes of the CPU tests: meshes of every count around the largest leaf and
 // around a workgroup, identical triangles, meshes flat on one, two and three axes, tiny, huge and denormal extents, sums
 // that overflow, NaN and infinite coordinates; at a cheap, the default and a dear inner node, through the ladder and with
 // a record limit.  Whatever the input: a code, or a tree whose leaves of 1..15 triangles are a partition, no deeper than
@@ -12,17 +12,7 @@
 #include <random>
 #include <vector>
 
-#include "halogen_abi.h"
-#include "hg_lbvh.h"
-
-static int failures = 0;
-#define EXPECT(c)                                                      \
-    do {                                                               \
-        if (!(c)) {                                                    \
-            std::printf("FAILED %s:%d %s\n", __FILE__, __LINE__, #c); \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
+#include "lbvh_check.h"
 
 // Returns the inner entries of the tree, or -1
 static int64_t run(const std::vector<HalogenTriangle>& tris, float node_cost, int64_t max_records) {
@@ -49,41 +39,8 @@ static int64_t run(const std::vector<HalogenTriangle>& tris, float node_cost, in
     EXPECT(hg_build_blas_lbvh_sah(tris.data(), n, node_cost, max_records, order.data(), out.data(), nodes.data(), count,
                                   nullptr) == count);
     EXPECT(!std::memcmp(nodes.data(), all.data(), nodes.size() * sizeof(BVHEntry)));
-    std::vector<int> seen(size_t(n), 0);
-    for (int32_t k = 0; k < n; ++k) {
-        EXPECT(order[size_t(k)] >= 0 && order[size_t(k)] < n);
-        if (order[size_t(k)] < 0 || order[size_t(k)] >= n) return -1;
-        seen[size_t(order[size_t(k)])]++;
-        EXPECT(!std::memcmp(&out[size_t(k)], &tris[size_t(order[size_t(k)])], sizeof(HalogenTriangle)));
-    }
-    for (int s : seen) EXPECT(s == 1);
-    // the walk: every entry once, leaves of 1..15 a partition, depth inside the bound
-    std::vector<int> covered(size_t(n), 0);
-    std::vector<std::pair<uint32_t, uint32_t>> stack{{0u, 0u}};
-    size_t reached = 0;
-    uint32_t deepest = 0;
-    while (!stack.empty() && reached <= nodes.size()) {
-        const auto [g, d] = stack.back();
-        stack.pop_back();
-        ++reached;
-        deepest = std::max(deepest, d);
-        EXPECT(g < nodes.size());
-        if (g >= nodes.size()) return -1;
-        const BVHEntry& e = nodes[g];
-        if (e.triangleCount) {
-            EXPECT(e.triangleCount <= HG_LBVH_MAX_LEAF && uint64_t(e.indexA) + e.triangleCount <= uint64_t(n));
-            for (uint32_t t = e.indexA; t < e.indexA + e.triangleCount && t < uint32_t(n); ++t) covered[t]++;
-        } else {
-            stack.push_back({e.indexA + 1, d + 1});
-            stack.push_back({e.indexA, d + 1});
-        }
-    }
-    EXPECT(reached == nodes.size());
-    for (int s : covered) EXPECT(s == 1);
-    EXPECT(deepest <= hg_lbvh_depth_bound(uint32_t(n)) && deepest <= HG_LBVH_MAX_DEPTH);
-    std::vector<BVHEntry> again = nodes;
-    EXPECT(hg_refit_blas(out.data(), n, again.data(), int32_t(again.size())) == HG_OK);
-    EXPECT(!std::memcmp(again.data(), nodes.data(), nodes.size() * sizeof(BVHEntry)));
+    if (!check_order(tris, order, out)) return -1;
+    if (!check_tree(nodes, out, 1u, HG_LBVH_MAX_LEAF, uint32_t(n))) return -1;  // leaves of 1..15 a partition
     return (count - 1) / 2;
 }
 
@@ -96,17 +53,6 @@ static void run_all(const std::vector<HalogenTriangle>& tris) {
     if (inner > 0) run(tris, 0.0f, inner - 1);
     run(tris, 0.0f, 0);
     run(tris, 1e-6f, 0);
-}
-
-static std::vector<HalogenTriangle> make(std::mt19937& rng, int n, float lo, float hi, int flat_mask) {
-    std::uniform_real_distribution<float> pos(lo, hi);
-    std::vector<HalogenTriangle> t(static_cast<size_t>(n));
-    for (HalogenTriangle& h : t) {
-        float* p = &h.pointA.x;  // pointA, pointB, pointC: nine floats
-        for (int k = 0; k < 9; ++k) p[k] = (flat_mask >> (k % 3)) & 1 ? 0.25f : pos(rng);
-        h.normalA = h.normalB = h.normalC = {0.0f, 1.0f, 0.0f};
-    }
-    return t;
 }
 
 // small triangles around random centres: subtrees that are worth a leaf and subtrees that are not

@@ -6,16 +6,8 @@
 #include <cstdlib>
 #include <random>
 
+#include "expect.h"
 #include "mesh_trees_check.h"
-
-static int failures = 0;
-#define EXPECT(c)                                                      \
-    do {                                                               \
-        if (!(c)) {                                                    \
-            std::printf("FAILED %s:%d %s\n", __FILE__, __LINE__, #c); \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
 
 static bool starts(const std::string& s, const char* with) { return s.rfind(with, 0) == 0; }
 

@@ -1,6 +1,6 @@
 // asan_normals.cpp — the host side of recomputed vertex normals under AddressSanitizer + UBSan (make asan_normals;
 // tests/test_normals.py): the adjacency builder and the arithmetic of csrc/hg_normals.h and the twin hg_vertex_normals
-// (hg_host.cpp), on random and adversarial index lists.  Arrays are sized exactly, so a read or write past either end
+// (hg_host_mesh.cpp), on random and adversarial index lists.  Arrays are sized exactly: a read or write past either end
 // is an error here.  Whatever the input, every call must return a code, and a refused call must have written nothing.
 #include <algorithm>
 #include <cmath>
@@ -10,17 +10,9 @@
 #include <random>
 #include <vector>
 
+#include "expect.h"
 #include "halogen_abi.h"
 #include "hg_normals.h"
-
-static int failures = 0;
-#define EXPECT(c)                                                      \
-    do {                                                               \
-        if (!(c)) {                                                    \
-            std::printf("FAILED %s:%d %s\n", __FILE__, __LINE__, #c); \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
 
 // The adjacency of `idx` is what the header promises: every corner once, under its vertex, in triple order
 static void check_adjacency(const std::vector<int32_t>& idx, int nt, int nv) {

@@ -1,21 +1,13 @@
 // asan_refit.cpp — the host side of a refit under AddressSanitizer + UBSan (make asan_refit; tests/test_refit.py):
-// hg_refit_blas (hg_host.cpp), the refit plan (csrc/hg_refit_plan.h) and the upload decision after a refit
+// hg_refit_blas (hg_host_mesh.cpp), the refit plan (csrc/hg_refit_plan.h) and the upload decision after a refit
 // (csrc/hg_scene_pack.h), on builder output and on corrupted copies of it.  Whatever the input, every call must return
 // a code and touch nothing outside its arrays; on good input the refit of unchanged triangles changes nothing.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 
+#include "expect.h"
 #include "hg_scene_pack.h"
-
-static int failures = 0;
-#define EXPECT(c)                                                      \
-    do {                                                               \
-        if (!(c)) {                                                    \
-            std::printf("FAILED %s:%d %s\n", __FILE__, __LINE__, #c); \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
 
 struct Mesh {
     std::vector<HalogenTriangle> tris;

@@ -1,5 +1,5 @@
 // asan_skin.cpp — the host side of a deform from vertices under AddressSanitizer + UBSan (make asan_skin;
-// tests/test_skin.py): the skinning twin hg_skin_vertices (hg_host.cpp) and the checks hg_set_mesh_vertices and
+// tests/test_skin.py): the skinning twin hg_skin_vertices (hg_host_mesh.cpp) and the checks hg_set_mesh_vertices and
 // hg_set_mesh_skin make of the caller's lists before anything is bound (csrc/hg_skin.h), on random and edge input.
 // Arrays are sized exactly, so a read or write past either end is an error here.  Whatever the input, every call must
 // return a code, and a refused call must have written nothing.
@@ -9,17 +9,9 @@
 #include <random>
 #include <vector>
 
+#include "expect.h"
 #include "halogen_abi.h"
 #include "hg_skin.h"
-
-static int failures = 0;
-#define EXPECT(c)                                                      \
-    do {                                                               \
-        if (!(c)) {                                                    \
-            std::printf("FAILED %s:%d %s\n", __FILE__, __LINE__, #c); \
-            ++failures;                                                \
-        }                                                              \
-    } while (0)
 
 int main() {
     std::mt19937 rng(2468);

@@ -1,5 +1,5 @@
-// tsan_blas — ThreadSanitizer driver of the parallel BLAS builder (hg_build_blas_mt, csrc/hg_host.cpp), built with
-// g++ -fsanitize=thread straight from hg_host.cpp (make -C halogen-pathtracer_amd tsan; tests/test_sanitizers.py).
+// tsan_blas — ThreadSanitizer driver of the parallel BLAS builder (hg_build_blas_mt, csrc/hg_host_blas.cpp), built
+// with g++ -fsanitize=thread and the host sources (make -C halogen-pathtracer_amd tsan; tests/test_sanitizers.py).
 //
 //   tsan_blas N_TRIS SEED THREADS...
 // builds the BVH of a random triangle soup (N_TRIS >= 32,768 reaches the rank-parallel partition of large nodes)

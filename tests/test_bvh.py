@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import hg_oracle
+from bvh_cases import grid_ties, shuffled
 from halogen import abi
 from halogen.scenes import dragon_mesh
 from halogen.unity import mesh_bounds_min_max, unity_cube, unity_plane
@@ -84,10 +85,6 @@ def _build_mt(threads):
     return fn
 
 
-def _shuffled(t, seed):
-    return np.random.default_rng(seed).permutation(np.asarray(t)).astype(np.int32)
-
-
 @pytest.mark.parametrize("threads", [2, 5, 16])
 @pytest.mark.parametrize("mesh", ["dragon_x3", "dragon_x3_shuffled", "grid_ties"])
 def test_parallel_builder_equals_sequential(built, mesh, threads):
@@ -96,14 +93,9 @@ def test_parallel_builder_equals_sequential(built, mesh, threads):
     if mesh.startswith("dragon"):
         v, _, t = dragon_mesh(3)  # 78,408 triangles: the top levels take the rank-parallel partition
         if mesh.endswith("shuffled"):
-            t = _shuffled(t, 3)
+            t = shuffled(t, 3)
     else:  # a lattice of coincident centroids and +-0 coordinates: ties on the split plane and in the folds
-        g = np.stack(np.meshgrid(np.arange(-20, 21), np.arange(-20, 21), np.arange(-20, 21)), -1).reshape(-1, 3)
-        v = (g * 0.5).astype(np.float32)
-        v[v == 0] = -0.0
-        rng = np.random.default_rng(5)
-        t = rng.integers(0, len(v), size=(60000, 3)).astype(np.int32)
-        t[::7] = t[::7, :1]  # degenerate triangles: all three vertices equal
+        v, t = grid_ties()
     a, ia = _build(abi.lib().hg_build_blas, v, t)
     b, ib = _build(_build_mt(threads), v, t)
     assert np.array_equal(a, b), "node arrays differ"
@@ -111,7 +103,7 @@ def test_parallel_builder_equals_sequential(built, mesh, threads):
 
 
 def test_parallel_partition_rule_small_cases(built):
-    """The rank rule of the parallel partition (hg_host.cpp) against the two-pointer loop it restates, on every
+    """The rank rule of the parallel partition (hg_host_blas.cpp) against the two-pointer loop it restates, on every
     left/right pattern of length <= 10 (the C++ path only takes it for large nodes)."""
     import itertools
 

@@ -4,26 +4,20 @@ triangles (through the reference's Bounds arithmetic, thin boxes padded) and its
 index list is a permutation of the input triangles.  And the oracle, which traverses any hierarchy the reference's
 way, renders it with the same nearest hits as the reference's tree on a band of C3 (the image differs only where two
 triangles tie within rounding)."""
-import ctypes as C
+import json
+from pathlib import Path
 
 import numpy as np
 import pytest
 
-from halogen import abi
+import bvh_cases
 from halogen.scenes import dragon_mesh
 from halogen.unity import unity_cube, unity_plane
 
 HG_E_INVALID = -1  # include/halogen_abi.h
 
 
-def _sah(verts, tris, max_leaf=2, max_depth=48):
-    verts = np.ascontiguousarray(verts, np.float32)
-    idx = np.ascontiguousarray(tris, np.int32).copy()
-    cap = 2 * len(idx) + 2
-    nodes = (abi.BVHEntry * cap)()
-    n = abi.lib().hg_build_blas_sah(verts.ctypes.data, len(verts), idx.ctypes.data, len(idx), max_leaf, max_depth,
-                                    C.cast(nodes, C.c_void_p), cap)
-    return n, nodes, idx
+_sah = bvh_cases.build_sah
 
 
 def _check(verts, tris, n, nodes, idx, max_leaf, max_depth=48):
@@ -85,6 +79,15 @@ def test_sah_flat_and_degenerate_meshes():
     assert _sah(verts, tri, max_leaf=0)[0] == HG_E_INVALID
     assert _sah(verts, tri, max_leaf=16)[0] == HG_E_INVALID
     assert _sah(verts, np.array([[0, 1, 7]], np.int32))[0] == HG_E_INVALID
+
+
+def test_sah_trees_are_the_recorded_ones():
+    """The exact trees (README's image comparison and bench.py's SAH leg rest on them): the entries and the index list
+    of every pinned mesh at max_leaf 2 and 4, digest for digest those recorded in tests/golden/blas_sah_digests.json."""
+    want = json.loads((Path(__file__).parent / "golden" / "blas_sah_digests.json").read_text())
+    got = bvh_cases.sah_digests()
+    assert len(want) == 10 and got == want, {k: (got.get(k), want.get(k)) for k in set(got) | set(want)
+                                              if got.get(k) != want.get(k)}
 
 
 def test_sah_oracle_band_same_hits_as_reference_tree():

@@ -2,21 +2,10 @@
 (host/asan_cull_table.cpp, make asan_cull_table): hand-made scenes with a leaf root, a singular matrix, 70 meshes, no
 cullable mesh and an odd number of entries, their partial re-uploads, and seeded synthetic mesh tables, each table
 checked and then walked two entries per fetch, as the kernel walks it, for every launch length.  Host code only."""
-import os
-import subprocess
-from pathlib import Path
-
-ROOT = Path(__file__).resolve().parents[1]
-PKG = ROOT / "halogen-pathtracer_amd"
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+from host_programs import run_sanitizer_program
 
 
 def test_cull_table_under_asan_ubsan():
-    subprocess.run(["make", "-s", "-C", str(PKG), "asan_cull_table"], check=True)
-    r = subprocess.run([str(PKG / "build" / "asan_cull_table"), "200", "5"], capture_output=True, text=True, env=ENV,
-                       timeout=300)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out
+    out = run_sanitizer_program("asan_cull_table", 200, 5)
     assert "hand-made scenes done" in out and out.rstrip().endswith("cull table ok"), out
     assert "FAILED" not in out and "runtime error" not in out, out

@@ -1,21 +1,18 @@
-"""The display denoiser on the host (hg_denoise_host, csrc/hg_host.cpp over csrc/hg_atrous.h): the edge-avoiding a-trous
-filter of include/halogen_abi.h against its numpy float32 restatement (tests/denoise_ref.py), bit for bit; exact
+"""The display denoiser on the host (hg_denoise_host, csrc/hg_host_denoise.cpp over csrc/hg_atrous.h): the edge-avoiding
+a-trous filter of include/halogen_abi.h against its numpy float32 restatement (tests/denoise_ref.py), bit for bit; exact
 properties of the contract; rejected parameters; the filter under AddressSanitizer + UBSan as a stand-alone program.
 
 The device path is held to hg_denoise_host by tests/test_gpu_denoise.py."""
 import ctypes as C
 import itertools
-import os
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import denoise_ref as ref
 from halogen import abi
+from host_programs import run_sanitizer_program
 
-ROOT = Path(__file__).resolve().parents[1]
 F = np.float32
 W, H = 37, 23  # not a multiple of 8, and narrower than 2 * step from iteration 4 on: every border case occurs
 
@@ -142,12 +139,7 @@ def test_rejected_parameters(built):
 def test_host_filter_under_asan_ubsan():
     """hg_denoise_host as a stand-alone program built with -fsanitize=address,undefined from the host sources: 1x1, 1x7,
     7x1 and 37x23 images in exactly sized buffers, every term on and off, 1..6 iterations."""
-    subprocess.run(["make", "-s", "-C", str(ROOT / "halogen-pathtracer_amd"), "asan_denoise"], check=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(ROOT / "halogen-pathtracer_amd" / "build" / "asan_denoise"), "11"], env=env,
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
+    out = run_sanitizer_program("asan_denoise", 11)
     for size in ("1x1", "1x7", "7x1", "37x23"):
-        assert f"{size}: 6 iteration counts x 16 settings, finite" in r.stdout, r.stdout
-    assert "bad parameters rejected" in r.stdout
+        assert f"{size}: 6 iteration counts x 16 settings, finite" in out, out
+    assert "bad parameters rejected" in out

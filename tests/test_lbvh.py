@@ -5,8 +5,6 @@ result (hg_refit_blas, hg_pack_geometry through tests/test_scene_pack.py's drive
 assertion that the input is the edge it claims to be; the host sanitizer program (make asan_lbvh).  The device build is
 tests/test_gpu_rebuild.py's."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -14,11 +12,10 @@ import pytest
 import lbvh_cases
 from halogen import abi
 from halogen.scene import PackedScene
+from host_programs import run_sanitizer_program
 from test_refit import BVH_DT, as_np, assert_same_nodes, refit_native, refit_numpy, tris_np
 from test_scene_pack import driver, mesh as mesh_record, parse, write_scene  # noqa: F401 (driver: a fixture)
 
-ROOT = Path(__file__).resolve().parents[1]
-PKG = ROOT / "halogen-pathtracer_amd"
 f32, u32 = np.float32, np.uint32
 LEAF_SIZES = (1, 4, 15)
 
@@ -299,6 +296,4 @@ def test_key_point_at_pmax_is_cell_1023():
 def test_asan_lbvh_program():
     """host/asan_lbvh.cpp under AddressSanitizer + UBSan: hg_build_blas_lbvh on the input classes above (make
     asan_lbvh; a stand-alone program, host code only)."""
-    subprocess.run(["make", "-s", "-C", str(PKG), "asan_lbvh"], check=True)
-    r = subprocess.run([str(PKG / "build" / "asan_lbvh")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "asan_lbvh ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert "asan_lbvh ok" in run_sanitizer_program("asan_lbvh")

@@ -6,7 +6,6 @@ entries; boxes by tests/test_refit.py's restatement.  Then the structure of the 
 the refusals and the host sanitizer program (make asan_lbvh_sah).  The device build is tests/test_gpu_rebuild_sah.py's."""
 import ctypes as C
 import re
-import subprocess
 from functools import lru_cache
 from pathlib import Path
 
@@ -16,6 +15,7 @@ import pytest
 import lbvh_cases
 from halogen import abi
 from halogen.scene import PackedScene
+from host_programs import run_sanitizer_program
 from test_refit import BVH_DT, as_np, assert_same_nodes, refit_native, refit_numpy, tris_np
 from test_scene_pack import driver, mesh as mesh_record, parse, write_scene  # noqa: F401 (driver: a fixture)
 
@@ -388,6 +388,4 @@ def test_deform_rebuild_sah_keeps_pack_current():
 def test_asan_lbvh_sah_program():
     """host/asan_lbvh_sah.cpp under AddressSanitizer + UBSan: hg_build_blas_lbvh_sah on the input classes above (make
     asan_lbvh_sah; a stand-alone program, host code only)."""
-    subprocess.run(["make", "-s", "-C", str(PKG), "asan_lbvh_sah"], check=True)
-    r = subprocess.run([str(PKG / "build" / "asan_lbvh_sah")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "asan_lbvh_sah ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert "asan_lbvh_sah ok" in run_sanitizer_program("asan_lbvh_sah")

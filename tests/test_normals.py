@@ -4,7 +4,6 @@ matter; refusals; RayTracingMesh.deform / pose with normals="recompute"; the con
 sanitizer program (make asan_normals).  The entry points that need a context are tests/test_gpu_normals.py's."""
 import ctypes as C
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -14,9 +13,9 @@ import deform_cases as dc
 import normals_cases as nc
 import refit_cases
 from halogen import abi
+from host_programs import run_sanitizer_program
 
 ROOT = Path(__file__).resolve().parents[1]
-PKG = ROOT / "halogen-pathtracer_amd"
 f32 = np.float32
 
 
@@ -203,6 +202,4 @@ def test_python_constants_match_the_sources(built):
 def test_asan_normals_program():
     """host/asan_normals.cpp under AddressSanitizer + UBSan: the adjacency builder, the shared arithmetic and
     hg_vertex_normals on random and adversarial lists (make asan_normals; a stand-alone program, host code only)."""
-    subprocess.run(["make", "-s", "-C", str(PKG), "asan_normals"], check=True)
-    r = subprocess.run([str(PKG / "build" / "asan_normals")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "asan_normals ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert "asan_normals ok" in run_sanitizer_program("asan_normals")

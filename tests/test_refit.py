@@ -13,6 +13,7 @@ import pytest
 
 from halogen import abi, scene as hs, scenes
 from halogen.unity import Transform, unity_cube, unity_plane
+from host_programs import run_sanitizer_program
 
 ROOT = Path(__file__).resolve().parents[1]
 PKG = ROOT / "halogen-pathtracer_amd"
@@ -483,6 +484,4 @@ def test_upload_decision_after_a_refit(driver):
 def test_asan_refit_program():
     """host/asan_refit.cpp under AddressSanitizer + UBSan: hg_refit_blas, the plan and the decision on adversarial
     input (make asan_refit; a stand-alone program, host code only)."""
-    subprocess.run(["make", "-s", "-C", str(PKG), "asan_refit"], check=True)
-    r = subprocess.run([str(PKG / "build" / "asan_refit")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "asan_refit ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert "asan_refit ok" in run_sanitizer_program("asan_refit")

@@ -5,7 +5,7 @@ available on this pool, so the HIP kernels are covered by the bit-exact parity t
   sanitize), rendering golden cases on several pthreads: no report, and the image bit-identical to the regular
   oracle build's;
 - the oracle's BVH builder (BVHGenerator.cs restated) under the same sanitizers;
-- the product's parallel BLAS builder hg_build_blas_mt (std::thread pool, atomics; csrc/hg_host.cpp) under
+- the product's parallel BLAS builder hg_build_blas_mt (std::thread pool, atomics; csrc/hg_host_blas.cpp) under
   ThreadSanitizer (halogen-pathtracer_amd/host/tsan_blas.cpp, make -C halogen-pathtracer_amd tsan), large enough to
   take the rank-parallel partition, with 2, 5 and 16 workers: no data race, output equal to the sequential build."""
 import os
@@ -18,26 +18,17 @@ import pytest
 import cases
 import hg_oracle
 from halogen import host_files
+from host_programs import ENV as SANITIZER_ENV, run_sanitizer_program
 
 ROOT = Path(__file__).resolve().parents[1]
 ASAN = ROOT / "oracle" / "build" / "hg_oracle_asan"
-TSAN = ROOT / "halogen-pathtracer_amd" / "build" / "tsan_blas"
-ASAN_SAH = ROOT / "halogen-pathtracer_amd" / "build" / "asan_sah"
-ASAN_SCENE_PACK = ROOT / "halogen-pathtracer_amd" / "build" / "asan_scene_pack"
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1", TSAN_OPTIONS="halt_on_error=1:exitcode=66")
+ENV = dict(os.environ, **SANITIZER_ENV)
 
 
 @pytest.fixture(scope="module")
 def asan():
     subprocess.run(["make", "-s", "-C", str(ROOT / "oracle"), "sanitize"], check=True)
     return ASAN
-
-
-@pytest.fixture(scope="module")
-def tsan():
-    subprocess.run(["make", "-s", "-C", str(ROOT / "halogen-pathtracer_amd"), "tsan"], check=True)
-    return TSAN
 
 
 def run(cmd):
@@ -66,8 +57,8 @@ def test_oracle_bvh_builder_under_asan_ubsan(asan):
     assert "BVH entries" in run([asan, "blas", 20000, 3])
 
 
-def test_parallel_blas_builder_under_tsan(tsan):
-    out = run([tsan, 40000, 7, 2, 5, 16])
+def test_parallel_blas_builder_under_tsan():
+    out = run_sanitizer_program("tsan", 40000, 7, 2, 5, 16)
     assert out.count("identical") == 3
 
 
@@ -101,12 +92,11 @@ def test_host_pool_under_tsan(tmp_path):
 
 
 def test_sah_builder_under_asan_ubsan():
-    """hg_build_blas_sah (the non-reference SAH hierarchy, csrc/hg_host.cpp) under AddressSanitizer + UBSan: random
+    """hg_build_blas_sah (the non-reference SAH hierarchy, csrc/hg_host_sah.cpp) under AddressSanitizer + UBSan: random
     soups, a flat grid (every box thin, padded), coincident triangles, an empty mesh, denormal and near-FLT_MAX
     coordinates (-fsanitize=float-cast-overflow: no bin conversion out of range); every triangle in one leaf; a NaN or
     infinite vertex rejected."""
-    subprocess.run(["make", "-s", "-C", str(ROOT / "halogen-pathtracer_amd"), "asan_sah"], check=True)
-    out = run([ASAN_SAH, 20000, 7])
+    out = run_sanitizer_program("asan_sah", 20000, 7)
     assert out.count("every triangle in one leaf") == 12, out
     assert out.count("non-finite vertex rejected") == 2, out
 
@@ -117,7 +107,6 @@ def test_scene_pack_under_asan_ubsan():
     text, 300 seeded random scenes checked by the host walk (host/scene_pack_check.h), and 8 single-field corruptions
     of each (a mesh offset, an indexA or a triangleCount replaced by a random value), every one of them rejected or
     packed into a scene whose refs, table indices and triangle ranges the walk finds in bounds."""
-    subprocess.run(["make", "-s", "-C", str(ROOT / "halogen-pathtracer_amd"), "asan_scene_pack"], check=True)
-    out = run([ASAN_SCENE_PACK, 300, 11])
+    out = run_sanitizer_program("asan_scene_pack", 300, 11)
     assert "hand-made trees and rejections done" in out and out.rstrip().endswith("scene pack ok"), out
     assert "FAILED" not in out, out

@@ -4,7 +4,6 @@ constants the Python layer mirrors; the host sanitizer program (make asan_skin).
 are tests/test_gpu_deform.py's."""
 import ctypes as C
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 import deform_cases as dc
 import refit_cases
 from halogen import abi
+from host_programs import run_sanitizer_program
 
 ROOT = Path(__file__).resolve().parents[1]
 PKG = ROOT / "halogen-pathtracer_amd"
@@ -158,6 +158,4 @@ def test_python_constants_match_the_sources(built):
 def test_asan_skin_program():
     """host/asan_skin.cpp under AddressSanitizer + UBSan: hg_skin_vertices and the checks of a binding's lists on random
     and edge input (make asan_skin; a stand-alone program, host code only)."""
-    subprocess.run(["make", "-s", "-C", str(PKG), "asan_skin"], check=True)
-    r = subprocess.run([str(PKG / "build" / "asan_skin")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "asan_skin ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert "asan_skin ok" in run_sanitizer_program("asan_skin")
