@@ -3,11 +3,16 @@
  * checker (tests/, __graft_entry__.smoke) and as bench.py's cpu_baseline.  The product path
  * (libhalogen_hip.so) never links, loads or calls anything under oracle/.
  *
- * Parity status: UNPINNED against the reference's own outputs — the reference (HLSL + C# in Unity) has
+ * Parity status: no output of the reference itself pins this file — the reference (HLSL + C# in Unity) has
  * no tests, no golden images and cannot be compiled or run in this image (no dxc/Unity/dotnet).  What is
  * pinned: the Sobol direction table (against the Joe–Kuo construction and against the table text in
  * HalogenRandom.hlsl:10-46, tests/golden/sobol_table.json), the sampler hashes (against an independent
- * numpy restatement), and the transcendental spec (include/hg_fmath.h, against libm to <= 2 ulp).
+ * numpy restatement), the transcendental spec (include/hg_fmath.h, against libm to <= 2 ulp), and, against
+ * float64 references and closed forms that share no code with it (tests/truth.py, tests/test_truth.py): the
+ * triangle, box and sphere tests, the closest hit over instanced meshes, the sampler's net properties, reflection,
+ * refraction, Schlick, the diffuse scatter, the cube face selection and the image of a diffuse object under a
+ * constant sky.  Not pinned by anything but this restatement: the medium stack, Beer absorption, the specular and
+ * transmissive branches of material_brdf, the camera, and the cube seams and filtering.
  */
 #ifndef HG_ORACLE_H
 #define HG_ORACLE_H

@@ -1,8 +1,8 @@
 """TEST INFRASTRUCTURE ONLY — ctypes binding of the CPU oracle (oracle/hg_oracle.c).
 
 Importable only by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.  The oracle is the parity
-checker and the CPU baseline; the product path never touches it.  PARITY UNPINNED against reference outputs
-(the reference has none and cannot run here) — see oracle/hg_oracle.h.
+checker and the CPU baseline; the product path never touches it.  No output of the reference pins it (the reference
+has none and cannot run here); what float64 references and closed forms pin, and what they do not: oracle/hg_oracle.h.
 """
 from __future__ import annotations
 
